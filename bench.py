@@ -6,7 +6,15 @@ HybridLoss terms L1 + SSIM + Phys_srgb, global-norm clip 0.01 + AdamW.  One "ste
 (+ bucketed RCCL all-reduce when N > 1) + clip + AdamW, all HIP kernels.  Default precision fp16 (fp16 storage and
 MFMA operands, fp32 accumulation / statistics / parameters, dynamic loss scaling): the reference's AMP dtype.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp16|bf16|fp32] [--workload cfg2|cfg3|cfg4] [--quick]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp16|bf16|fp32] [--workload cfg2|cfg3|cfg4|cfg5]
+                    [--dump-outputs DIR] [--full [--quick] [--no-cpu-baseline]]
+
+A plain run does only what the headline needs: set-up, W eager warm-up steps, graph capture, K timed steps, the
+optional output dump, and the result line (metric / value / unit / higher_is_better / dtype / ms_per_step / losses).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/output.npy and DIR/losses.npy (dump_outputs);
+weights, inputs and seeds depend on the arguments alone, so two builds can be compared output for output.
+`--full` adds every other figure listed below (K profiled eager steps ahead of the timed ones, the comparisons with
+the CPU oracle, the other modes and workloads, the CPU baseline); `--quick` / `--no-cpu-baseline` trim it.
 
 N > 1 runs one process per GPU.  Either under a launcher (python -m torch.distributed.run --nproc-per-node N
 --master-addr 127.0.0.1 bench.py --gpus N ...: WORLD_SIZE must equal N, else the bench exits non-zero), or stand-alone
@@ -16,7 +24,7 @@ contract of NAFNet_base/basicsr/train.py:54-63, utils/dist_util.py:28-40), befor
 with the first failing rank's status.  Fewer visible GPUs than N is an error (NBP_BENCH_REHEARSE=1 excepted: every
 rank on cuda:0 over gloo, a rehearsal of the N > 1 path on a one-GPU box, tagged in the JSON line).
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  With `--full` it also carries:
 * `roofline`: the dominant kernel class (by measured time among the classes below), timed live with HIP events on
   the launch stream over K eager steps; achieved = its algorithmic bytes (or FLOPs) per launch / its average launch
   duration.  Classes: `gemm16` (every 16-bit MFMA GEMM entry: nbp_gemm_bf16 + the fused-epilogue entries
@@ -595,54 +603,12 @@ def spawn_ranks(n, argv):
     return status
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=None, help="GPUs = ranks (default: WORLD_SIZE under a launcher, else 1)")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="headline only: no extra modes / cfg3 / CPU baseline")
-    ap.add_argument("--eager", action="store_true", help="time eager launches instead of HIP-graph replays")
-    ap.add_argument("--precision", default="fp16", choices=["fp16", "bf16", "fp32"],
-                    help="fp16 (default; the reference's AMP dtype) / bf16: 16-bit storage + MFMA operands, fp32 "
-                         "accumulation; fp32: fp32 everywhere (parity mode)")
-    ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override (diagnostics; 0 = the workload's)")
-    args = ap.parse_args()
-    wl = WORKLOADS[args.workload]
-    BATCH, IMG = (args.batch or wl["batch"]), wl["img"]
-
-    # NBP_BENCH_REHEARSE=1 (one-GPU box only, never the measurement): every rank on cuda:0 over gloo, to exercise the
-    # N > 1 path (graph segments + bucket all-reduces, barriers, max-over-ranks timing) where RCCL needs one GPU per rank
-    rehearse = os.environ.get("NBP_BENCH_REHEARSE") == "1"
-    # counting devices does not initialise the GPU on this image (its documented behaviour; the parent of spawned ranks
-    # makes no other GPU call and starts its ranks as child processes, no exec; success path recorded in
-    # profiles/r05_rehearsal/)
-    how, world = plan_launch(args.gpus, os.environ, torch.cuda.device_count(), rehearse)
-    if how == "spawn":
-        sys.exit(spawn_ranks(world, sys.argv[1:]))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if rehearse:
-        local = 0
-    if world > 1:
-        torch.cuda.set_device(local)
-        if rehearse:
-            dist.init_process_group("gloo")
-        else:
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    dev = torch.device("cuda", local)
-
+def profiled_steps(tr, inputs, steps, world):
+    """--full: `steps` eager steps under the live profilers, ahead of the timed region.  Returns what the roofline
+    figures are computed from (roofline_fields)."""
     from lowlight_image_enhancement_amd import _lib
-
-    tr, init_sd = make_trainer(dev, args.workload, args.precision)
     net = tr.net
-    lq, gt, short, ratio = batch(dev, BATCH, IMG, rank)
-
-    for _ in range(args.warmup):
-        tr.step(lq, gt, short, ratio)
-    tr.logs()
-
+    lq, gt, short, ratio = inputs
     # live per-launch timing (HIP events on the launch stream) over K eager steps; each record carries the launch's
     # algorithmic FLOPs and HBM bytes (operands read once, outputs written once)
     prof = {}
@@ -674,7 +640,7 @@ def main():
     step_events = []
     _lib.launch_timing(True)  # the one-kernel classes: events around each of their launches inside the library
     tr.comm_probe = world > 1  # the eager steps' exposed all-reduce time (not NAFBlock time, not the rest either)
-    for _ in range(args.steps):
+    for _ in range(steps):
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -692,6 +658,85 @@ def main():
     net._block_fwd, net._block_bwd = orig_fwd, orig_bwd
     eager_comm = tr.comm_stats() if world > 1 else None
     tr.comm_probe, tr.comm_events = False, []
+    return {"prof": prof, "inst": inst, "blk_events": blk_events, "step_events": step_events, "eager_comm": eager_comm}
+
+
+DUMP_MAX_ELEMS = 12_000_000  # per dumped array, as float32: 48 MB, under the 64 MB the whole dump may take
+
+
+def dump_outputs(path, out, logs):
+    """--dump-outputs DIR: what a caller of the timed path received from its last step, for comparing two builds
+    output for output (same arguments = same seeds = same inputs).
+    output.npy: the restored batch the step returned, float32 [B, 3, H, W]; an output of more than DUMP_MAX_ELEMS
+                elements (cfg5) is written as a fixed sample instead: the elements at DUMP_MAX_ELEMS distinct indices
+                (the head of a seed-0 permutation), ascending, 1-D.
+    losses.npy: the step's loss dict (NBPTrainer.logs(): loss terms, Total, grad_norm, loss_scale), float64, in
+                sorted key order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    o = out.detach()
+    if o.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(o.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+        o = o.reshape(-1)[idx.to(o.device)]
+    np.save(os.path.join(path, "output.npy"), o.float().cpu().numpy())
+    np.save(os.path.join(path, "losses.npy"),
+            np.array([logs[k] for k in sorted(logs) if k != "skipped"], dtype=np.float64))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=None, help="GPUs = ranks (default: WORLD_SIZE under a launcher, else 1)")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the profiled eager steps (roofline / nafblock_roofline / comm), PSNR vs "
+                         "the CPU oracle, the other precision modes, cfg3 / cfg4 / cfg5 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--quick", action="store_true", help="with --full: no extra modes / cfg3 / cfg4 / cfg5 / CPU baseline")
+    ap.add_argument("--eager", action="store_true", help="time eager launches instead of HIP-graph replays")
+    ap.add_argument("--precision", default="fp16", choices=["fp16", "bf16", "fp32"],
+                    help="fp16 (default; the reference's AMP dtype) / bf16: 16-bit storage + MFMA operands, fp32 "
+                         "accumulation; fp32: fp32 everywhere (parity mode)")
+    ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
+    ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override (diagnostics; 0 = the workload's)")
+    args = ap.parse_args()
+    wl = WORKLOADS[args.workload]
+    BATCH, IMG = (args.batch or wl["batch"]), wl["img"]
+
+    # NBP_BENCH_REHEARSE=1 (one-GPU box only, never the measurement): every rank on cuda:0 over gloo, to exercise the
+    # N > 1 path (graph segments + bucket all-reduces, barriers, max-over-ranks timing) where RCCL needs one GPU per rank
+    rehearse = os.environ.get("NBP_BENCH_REHEARSE") == "1"
+    # counting devices does not initialise the GPU on this image (its documented behaviour; the parent of spawned ranks
+    # makes no other GPU call and starts its ranks as child processes, no exec; success path recorded in
+    # profiles/r05_rehearsal/)
+    how, world = plan_launch(args.gpus, os.environ, torch.cuda.device_count(), rehearse)
+    if how == "spawn":
+        sys.exit(spawn_ranks(world, sys.argv[1:]))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if rehearse:
+        local = 0
+    if world > 1:
+        torch.cuda.set_device(local)
+        if rehearse:
+            dist.init_process_group("gloo")
+        else:
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+    dev = torch.device("cuda", local)
+
+    tr, init_sd = make_trainer(dev, args.workload, args.precision)
+    net = tr.net
+    lq, gt, short, ratio = batch(dev, BATCH, IMG, rank)
+
+    for _ in range(args.warmup):
+        tr.step(lq, gt, short, ratio)
+    tr.logs()
+
+    # --full: K profiled eager steps ahead of the timed ones (the roofline figures' raw material)
+    profiled = profiled_steps(tr, (lq, gt, short, ratio), args.steps, world) if args.full else None
 
     # graph replay at every world size (N > 1: segments cut at the gradient buckets, all-reduces between them); a
     # rank whose capture fails falls back to eager steps, which issue the same collective sequence
@@ -712,8 +757,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        run(lq, gt, short, ratio)
+        out = run(lq, gt, short, ratio)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -722,8 +768,13 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    step_ms = elapsed / args.steps * 1e3
+    logs = tr.logs()  # of the last timed step
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, logs)
     comm = None
-    if world > 1:
+    if args.full and world > 1:
+        eager_comm = profiled["eager_comm"]
         # after the timed region: a few probed steps of the same kind (events on the compute stream around the bucket
         # waits, after the last backward segment) -> the all-reduce time the backward left exposed
         tr.comm_probe = True
@@ -734,8 +785,69 @@ def main():
         comm["allreduce_exposed_ms_eager"] = eager_comm["allreduce_exposed_ms"]
         comm["note"] = ("exposed = compute-stream time from the end of the last backward kernel to the completion of "
                         "every bucket all-reduce (graph replays; _eager: the profiled eager steps); rank 0's view")
-    logs = tr.logs()
+        logs = tr.logs()  # the line's losses are those of the last step run, here the last probed one
 
+    if rank == 0:
+        res = {
+            "metric": METRIC if args.workload == "cfg2" else f"training images/sec ({args.workload})",
+            "value": round(BATCH * world * args.steps / elapsed, 3),
+            "unit": "img/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(step_ms, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": {"bf16": "bf16", "fp16": "f16", "fp32": "f32"}[args.precision],
+            "data": "synthetic (U[0,1) sRGB, expo_ratio 1, torch default init, seed 0+rank)",
+            "config": {"workload": wl["desc"], "global_batch": BATCH * world, "image": IMG,
+                       "parallelism": f"dp{world}", "precision": args.precision,
+                       "launch": "hip-graph replay" if use_graph else "eager",
+                       **({"rehearsal": "gloo, every rank on cuda:0 (not a measurement)"} if rehearse else {})},
+            "losses": logs,
+        }
+        if args.full:
+            res.update(roofline_fields(profiled, comm, args, step_ms, world,
+                                       nafblock_bytes(net, BATCH, IMG, IMG, ESIZE[args.precision])))
+        if comm is not None:
+            res["comm"] = comm
+        if args.full and "raw_ratios" in wl:
+            res["phys_cons_raw"] = raw_metric(tr, (lq, gt, short, ratio), wl["raw_ratios"])
+        if args.full and world == 1:
+            res["psnr_vs_cpu_ref_db"], res["max_abs_vs_cpu_ref"] = psnr_vs_cpu(net, dev, IMG)
+            res["psnr_active_blocks_db"], res["max_abs_active_blocks"] = psnr_vs_cpu(net, dev, IMG, active=True)
+            if not args.quick and args.workload == "cfg2":
+                del tr, net
+                torch.cuda.empty_cache()
+                print("[bench] extra modes", file=sys.stderr, flush=True)
+                res["modes"] = {p: short_run(dev, "cfg2", p) for p in ("fp32", "bf16", "fp16") if p != args.precision}
+                print("[bench] cfg3 sample", file=sys.stderr, flush=True)
+                res["cfg3"] = dict(short_run(dev, "cfg3", args.precision, steps=3, warmup=2),
+                                   workload=WORKLOADS["cfg3"]["desc"], global_batch=WORKLOADS["cfg3"]["batch"])
+                print("[bench] cfg4 N=1 line", file=sys.stderr, flush=True)
+                res["cfg4"] = dict(short_run(dev, "cfg4", args.precision, steps=5, warmup=3),
+                                   workload=WORKLOADS["cfg4"]["desc"], global_batch=WORKLOADS["cfg4"]["batch"],
+                                   note="the >= 6.5x scaling config at N = 1 (python bench.py --workload cfg4 "
+                                        "--gpus N starts N local ranks and times it at N GPUs)")
+                print("[bench] cfg5 N=1 line", file=sys.stderr, flush=True)
+                res["cfg5"] = dict(short_run(dev, "cfg5", args.precision, steps=3, warmup=2),
+                                   workload=WORKLOADS["cfg5"]["desc"], global_batch=WORKLOADS["cfg5"]["batch"],
+                                   note="BASELINE configs[4] per GPU (4 x 8 = bs 32 globally); python bench.py "
+                                        "--workload cfg5 --gpus 4 times it at 4 GPUs")
+                if not args.no_cpu_baseline:
+                    print("[bench] cpu baseline", file=sys.stderr, flush=True)
+                    res["cpu_baseline"] = cpu_baseline(init_sd)
+        print(json.dumps(res), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def roofline_fields(profiled, comm, args, step_ms, world, blk_bytes):
+    """--full: the `roofline` and `nafblock_roofline` fields of the result line, from the profiled eager steps
+    (profiled_steps) and the timed step."""
+    prof, inst, eager_comm = profiled["prof"], profiled["inst"], profiled["eager_comm"]
+    blk_events, step_events = profiled["blk_events"], profiled["step_events"]
     classes = {}
     for cls, recs in prof.items():
         ms = sum(e0.elapsed_time(e1) for *_, e0, e1 in recs)
@@ -788,12 +900,9 @@ def main():
     for d in per_level.values():
         d["blocks_fwd"] //= args.steps
         d["fwd_ms"], d["bwd_ms"] = round(d["fwd_ms"], 3), round(d["bwd_ms"], 3)
-    esize = ESIZE[args.precision]
-    blk_bytes = nafblock_bytes(net, BATCH, IMG, IMG, esize)
     # The eager per-block events include host-dispatch stalls at the small levels (the GPU outruns the launches
     # there); the NAFBlock GPU time is the timed step minus the non-NAFBlock part of the eager step (boundary convs,
     # down/up, loss head, optimizer: few large kernels, not dispatch-bound).
-    step_ms = elapsed / args.steps * 1e3
     # N > 1: the exposed all-reduce time is neither NAFBlock nor the rest of the step: it leaves the eager
     # non-block part and the timed step alike
     exp_eager = (eager_comm or {}).get("allreduce_exposed_ms") or 0.0
@@ -801,67 +910,15 @@ def main():
     nonblock_ms = max(eager_step_ms - blk_ms - exp_eager, 0.0)
     blk_ms_gpu = max(step_ms - exp_graph - nonblock_ms, 1e-6)
     blk_gbps = blk_bytes / (blk_ms_gpu * 1e-3) / 1e9
-
-    if rank == 0:
-        res = {
-            "metric": METRIC if args.workload == "cfg2" else f"training images/sec ({args.workload})",
-            "value": round(BATCH * world * args.steps / elapsed, 3),
-            "unit": "img/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(step_ms, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": {"bf16": "bf16", "fp16": "f16", "fp32": "f32"}[args.precision],
-            "data": "synthetic (U[0,1) sRGB, expo_ratio 1, torch default init, seed 0+rank)",
-            "config": {"workload": wl["desc"], "global_batch": BATCH * world, "image": IMG,
-                       "parallelism": f"dp{world}", "precision": args.precision,
-                       "launch": "hip-graph replay" if use_graph else "eager",
-                       **({"rehearsal": "gloo, every rank on cuda:0 (not a measurement)"} if rehearse else {})},
-            "roofline": roof,
-            "nafblock_roofline": {"bytes_per_step": blk_bytes, "bytes_per_element": esize,
+    return {"roofline": roof,
+            "nafblock_roofline": {"bytes_per_step": blk_bytes, "bytes_per_element": ESIZE[args.precision],
                                   "ms_per_step": round(blk_ms_gpu, 3),
                                   "ms_method": "timed step - non-NAFBlock part of the eager step" + (
                                       " (both net of their exposed all-reduce time)" if world > 1 else ""),
                                   "eager_blocks_ms_per_step": round(blk_ms, 3),
                                   "per_level_eager": per_level,
                                   "achieved_GBps": round(blk_gbps, 1), "peak_GBps": HBM_PEAK_GBPS,
-                                  "frac": round(blk_gbps / HBM_PEAK_GBPS, 4)},
-            "losses": logs,
-        }
-        if comm is not None:
-            res["comm"] = comm
-        if "raw_ratios" in wl:
-            res["phys_cons_raw"] = raw_metric(tr, (lq, gt, short, ratio), wl["raw_ratios"])
-        if world == 1:
-            res["psnr_vs_cpu_ref_db"], res["max_abs_vs_cpu_ref"] = psnr_vs_cpu(net, dev, IMG)
-            res["psnr_active_blocks_db"], res["max_abs_active_blocks"] = psnr_vs_cpu(net, dev, IMG, active=True)
-            if not args.quick and args.workload == "cfg2":
-                del tr, net
-                torch.cuda.empty_cache()
-                print("[bench] extra modes", file=sys.stderr, flush=True)
-                res["modes"] = {p: short_run(dev, "cfg2", p) for p in ("fp32", "bf16", "fp16") if p != args.precision}
-                print("[bench] cfg3 sample", file=sys.stderr, flush=True)
-                res["cfg3"] = dict(short_run(dev, "cfg3", args.precision, steps=3, warmup=2),
-                                   workload=WORKLOADS["cfg3"]["desc"], global_batch=WORKLOADS["cfg3"]["batch"])
-                print("[bench] cfg4 N=1 line", file=sys.stderr, flush=True)
-                res["cfg4"] = dict(short_run(dev, "cfg4", args.precision, steps=5, warmup=3),
-                                   workload=WORKLOADS["cfg4"]["desc"], global_batch=WORKLOADS["cfg4"]["batch"],
-                                   note="the >= 6.5x scaling config at N = 1 (python bench.py --workload cfg4 "
-                                        "--gpus N starts N local ranks and times it at N GPUs)")
-                print("[bench] cfg5 N=1 line", file=sys.stderr, flush=True)
-                res["cfg5"] = dict(short_run(dev, "cfg5", args.precision, steps=3, warmup=2),
-                                   workload=WORKLOADS["cfg5"]["desc"], global_batch=WORKLOADS["cfg5"]["batch"],
-                                   note="BASELINE configs[4] per GPU (4 x 8 = bs 32 globally); python bench.py "
-                                        "--workload cfg5 --gpus 4 times it at 4 GPUs")
-                if not args.no_cpu_baseline:
-                    print("[bench] cpu baseline", file=sys.stderr, flush=True)
-                    res["cpu_baseline"] = cpu_baseline(init_sd)
-        print(json.dumps(res), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+                                  "frac": round(blk_gbps / HBM_PEAK_GBPS, 4)}}
 
 
 if __name__ == "__main__":

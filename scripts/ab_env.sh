@@ -7,6 +7,8 @@ export TMPDIR=/tmp
 OUT=$1
 shift
 mkdir -p gpurun_out/$OUT
+LOGS=${LOGS:-logs}/$OUT  # the arms' bench lines, their stderr and the ab.txt table
+mkdir -p "$LOGS"
 ROUNDS=${ROUNDS:-2}
 for r in $(seq $ROUNDS); do
   i=0
@@ -14,8 +16,8 @@ for r in $(seq $ROUNDS); do
     i=$((i + 1))
     envs=""
     [ "$e" != "-" ] && envs="$e"
-    env $envs timeout -k 10 300 python bench.py --quick --steps ${STEPS:-20} --warmup 5 > gpurun_out/$OUT/ab_${i}_r$r.json 2> gpurun_out/$OUT/ab_${i}_r$r.err || exit $?
-    v=$(python -c "import json,sys;d=json.load(open('gpurun_out/$OUT/ab_${i}_r$r.json'));print(d['value'],d['ms_per_step'],d['roofline']['kernel'],d['roofline']['frac'])")
-    echo "round $r  [$e]  $v" | tee -a gpurun_out/$OUT/ab.txt
+    env $envs timeout -k 10 300 python bench.py --full --quick --steps ${STEPS:-20} --warmup 5 > "$LOGS/ab_${i}_r$r.json" 2> "$LOGS/ab_${i}_r$r.err" || exit $?
+    v=$(python -c "import json,sys;d=json.load(open('$LOGS/ab_${i}_r$r.json'));print(d['value'],d['ms_per_step'],d['roofline']['kernel'],d['roofline']['frac'])")
+    echo "round $r  [$e]  $v" | tee -a "$LOGS/ab.txt"
   done
 done

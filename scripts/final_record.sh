@@ -17,10 +17,10 @@ SUFFIX=_$REC bash scripts/pmc_pass.sh > $O/pmc_pass.log 2>&1
 for p in fetch write mfma; do cp gpurun_out/pmc_${p}_$REC/run_kernel_stats.csv $O/pmc_${p}_kernel_stats.csv; done
 python scripts/pmc_traffic.py gpurun_out/pmc_fetch_$REC gpurun_out/pmc_write_$REC gpurun_out/pmc_mfma_$REC $O/pmc_traffic.json
 cp $O/pmc_traffic.json profiles/$REC/pmc_traffic.json
-timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench_stderr.txt
+timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench_stderr.txt
 tail -c 400 $O/bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$REC -o run --output-format csv -- \
-    python bench.py --steps 10 --warmup 3 --quick > $O/prof_bench.json 2> $O/prof_bench_stderr.txt
+    python bench.py --steps 10 --warmup 3 --full --quick > $O/prof_bench.json 2> $O/prof_bench_stderr.txt
 cp gpurun_out/prof_$REC/run_kernel_stats.csv $O/kernel_stats.csv
 python scripts/trace_levels.py gpurun_out/prof_$REC/run_kernel_trace.csv > $O/trace_levels.txt
 rm -rf gpurun_out/prof_$REC gpurun_out/pmc_*_$REC

@@ -21,10 +21,10 @@ STEPS=${STEPS:-smoke,pytest,bench,prof}
 KARGS=()
 [ -n "${PYTEST_K:-}" ] && KARGS=(-k "$PYTEST_K")
 [[ $STEPS == *pytest* ]] && run pytest_gpu 900 python -u -m pytest tests -m gpu -q -rf -p no:cacheprovider --timeout 300 --timeout-method thread "${KARGS[@]}"
-[[ $STEPS == *bench* ]] && run bench 600 python bench.py --steps 10 --warmup 3
+[[ $STEPS == *bench* ]] && run bench 600 python bench.py --full --steps 10 --warmup 3
 if [[ $STEPS == *prof* ]]; then
   export TMPDIR=/tmp
   run rocprof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- \
-      python bench.py --steps 5 --warmup 2 --no-cpu-baseline
+      python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline
 fi
 exit 0

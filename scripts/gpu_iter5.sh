@@ -17,6 +17,6 @@ if [ "${MICRO:-1}" = 1 ]; then
   cat $O/micro.txt
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 300 python bench.py --quick --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --quick --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
   python -c "import json,sys; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); print('value', d['value'], 'ms', d['ms_per_step'], 'nafblock', d['nafblock_roofline']['frac'], d['nafblock_roofline']['per_level_eager'])"
 fi

@@ -11,6 +11,8 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 tail -5 gpurun_out/r5a/pytest.log
 grep -h "near-ties" gpurun_out/r5a/pytest.log || true
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > gpurun_out/r5a/bench.json 2> gpurun_out/r5a/bench.err
-  tail -c 1500 gpurun_out/r5a/bench.json
+  LOGS=${LOGS:-logs/r5a}  # where the full bench line and its stderr go
+  mkdir -p "$LOGS"
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$LOGS/bench.json" 2> "$LOGS/bench.err"
+  tail -c 1500 "$LOGS/bench.json"
 fi

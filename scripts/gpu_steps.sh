@@ -23,9 +23,9 @@ STEPS=${STEPS:-smoke,pytest,bench}
 [[ ,$STEPS, == *,smoke,* ]] && run smoke 400 python -c "import __graft_entry__ as g; g.smoke()"
 [[ ,$STEPS, == *,newtests,* ]] && run newtests 600 "${PYT[@]}" ${NEWTESTS:-tests/test_gpu_loss_api.py}
 [[ ,$STEPS, == *,pytest,* ]] && run pytest_gpu 1000 "${PYT[@]}" tests -m gpu
-[[ ,$STEPS, == *,bench,* ]] && run bench 400 python bench.py --quick --steps 10 --warmup 3
-[[ ,$STEPS, == *,benchfull,* ]] && run benchfull 900 python bench.py
-[[ ,$STEPS, == *,rehearse,* ]] && run rehearse 400 env NBP_BENCH_REHEARSE=1 python bench.py --gpus 2 --quick --steps 5 --warmup 2
+[[ ,$STEPS, == *,bench,* ]] && run bench 400 python bench.py --full --quick --steps 10 --warmup 3
+[[ ,$STEPS, == *,benchfull,* ]] && run benchfull 900 python bench.py --full
+[[ ,$STEPS, == *,rehearse,* ]] && run rehearse 400 env NBP_BENCH_REHEARSE=1 python bench.py --gpus 2 --full --quick --steps 5 --warmup 2
 [[ ,$STEPS, == *,extra,* ]] && run extra 600 ${EXTRA}
 [[ ,$STEPS, == *,extra2,* ]] && run extra2 600 ${EXTRA2}
 [[ ,$STEPS, == *,extra3,* ]] && run extra3 600 ${EXTRA3}

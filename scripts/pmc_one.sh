@@ -7,5 +7,7 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out
 name=$1
 shift
+LOGS=${LOGS:-logs}  # the bench line and stderr of the pass
+mkdir -p "$LOGS"
 timeout -s KILL 300 rocprofv3 --pmc "$@" --kernel-trace --stats -d gpurun_out/pmc1_$name -o run --output-format csv \
-    -- python bench.py --steps 2 --warmup 1 --quick --eager > gpurun_out/pmc1_$name.log 2>&1
+    -- python bench.py --steps 2 --warmup 1 --full --quick --eager > "$LOGS/pmc1_$name.log" 2>&1

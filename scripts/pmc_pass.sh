@@ -10,7 +10,7 @@ mkdir -p gpurun_out
 PREC=${PREC:-fp16}
 WL=${WORKLOAD:-cfg2}
 SUF=${SUFFIX:-}
-BENCH="python bench.py --steps 3 --warmup 1 --quick --eager --precision $PREC --workload $WL"
+BENCH="python bench.py --steps 3 --warmup 1 --full --quick --eager --precision $PREC --workload $WL"
 pass() {
   local name=$1
   shift

@@ -12,7 +12,7 @@ for th in 16 32 16 32; do
   NBP_C1DW_BWD_TH=$th timeout -k 10 200 python scripts/c1dw_tile_micro.py 20 > $O/micro_th$th.txt 2>&1 || exit $?
   grep -E "bwd_new|C32|C64" $O/micro_th$th.txt
 done
-timeout -k 10 300 python bench.py --quick --steps 10 --warmup 3 > $O/bench.json 2> $O/bench_stderr.txt
+timeout -k 10 300 python bench.py --full --quick --steps 10 --warmup 3 > $O/bench.json 2> $O/bench_stderr.txt
 rc=$?
 tail -c 300 $O/bench.json
 exit $rc

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 O=gpurun_out/reduce_probe
 mkdir -p $O
 NBP_REDUCE_LOG=1 timeout -k 10 300 rocprofv3 --kernel-trace -d $O/prof -o run --output-format csv -- \
-    python bench.py --steps 1 --warmup 1 --quick --eager > $O/bench.json 2> $O/stderr.txt
+    python bench.py --steps 1 --warmup 1 --full --quick --eager > $O/bench.json 2> $O/stderr.txt
 grep "\[reduce\]" $O/stderr.txt > $O/log.txt || true
 python - <<'PY'
 import csv, glob

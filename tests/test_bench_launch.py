@@ -75,7 +75,7 @@ def test_rehearsal_line_carries_the_comm_fields():
     graph segments and bucket all-reduces; rank 0's JSON line reports the buckets and bytes all-reduced per step, the
     exposed all-reduce time of graph replays and of the eager steps, and the NAFBlock figure net of that time."""
     import json
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--quick"], {"NBP_BENCH_REHEARSE": "1"})
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--quick"], {"NBP_BENCH_REHEARSE": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["rehearsal"]
@@ -84,6 +84,46 @@ def test_rehearsal_line_carries_the_comm_fields():
     assert c["allreduce_exposed_ms"] is not None and c["allreduce_exposed_ms"] >= 0
     assert c["allreduce_exposed_ms_eager"] is not None and c["probed_steps"] >= 1
     assert "exposed all-reduce" in line["nafblock_roofline"]["ms_method"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_only_and_dumps_its_last_output(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline fields alone; --dump-outputs writes
+    what the last timed step returned (float32 output batch + float64 loss vector)."""
+    import json
+
+    import numpy as np
+    d = tmp_path / "dump"
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--dump-outputs", str(d)], {})
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "img/s" and line["higher_is_better"] is True and line["dtype"] == "f16"
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] - 2 * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]  # img/s = batch / step time
+    for k in ("roofline", "nafblock_roofline", "psnr_vs_cpu_ref_db", "modes", "cfg3", "cfg4", "cfg5", "cpu_baseline"):
+        assert k not in line, k
+    out = np.load(d / "output.npy")
+    assert out.dtype == np.float32 and out.shape == (2, 3, 256, 256) and np.isfinite(out).all()
+    losses = np.load(d / "losses.npy")
+    assert losses.dtype == np.float64
+    assert losses.tolist() == [line["losses"][k] for k in sorted(line["losses"]) if k != "skipped"]
+    assert sorted(p.name for p in d.iterdir()) == ["losses.npy", "output.npy"]
+    # --steps really sets the number of timed steps: the same run with one step fewer ends one optimizer update
+    # earlier, so its last output (same inputs, other weights) and its losses differ
+    d1 = tmp_path / "dump1"
+    r1 = _run(["--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "2", "--dump-outputs", str(d1)], {})
+    assert r1.returncode == 0, r1.stderr[-3000:]
+    line1 = json.loads([ln for ln in r1.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line1["steps"] == 1
+    out1 = np.load(d1 / "output.npy")
+    assert out1.shape == out.shape and not np.array_equal(out1, out)
+    assert not np.array_equal(np.load(d1 / "losses.npy"), losses)
+
+
+def test_full_and_dump_outputs_are_options():
+    r = _run(["--help"], {})
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
 
 
 def _newest_kernel_stats():
