@@ -348,6 +348,30 @@ int nbp_sca_dw_bwd(const void* dh, const float* a, const float* da_slab, int chu
                    float* dwsca, float* dbsca, const void* t2, const void* t1, const float* wdw, void* dt1, float* dwdw,
                    float* dbdw, float* ws, int B, int H, int W, int C, int dtype, nbp_stream_t s);
 
+/* TLSC local-window SCA for full-resolution inference (NAFNetLocal, NAFNet_arch.py:164-174; the test-time local
+ * converter's AvgPool2d, local_arch.py:29-76, its exact non-fast_imp path; Chu et al. 2021).  Where a block's window
+ * (k1, k2) = (min(H, k[0]), min(W, k[1])) does not cover its map, the SCA's pooled vector becomes a per-pixel map:
+ * V[b][iv][jv][c] = mean of g over the k1 x k2 window at (iv, jv), iv < _h = H - k1 + 1, jv < _w = W - k2 + 1
+ * (local_arch.py:61-67), replicate-padded to H x W with (H - _h) / 2 rows on top and (W - _w) / 2 columns on the left
+ * (:69-74): pooled[i][j] = V[clamp(i - (H - _h) / 2, 0, _h - 1)][clamp(j - (W - _w) / 2, 0, _w - 1)].  Windows stay
+ * inside one image of the batch.  Inference only (no backward).
+ * nbp_tlsc_supported: 1 for the shapes served (C a multiple of 4 in fp32 and of 8 in the 16-bit modes, C <= 1024,
+ * 1 <= k1 <= H, 1 <= k2 <= W, H and B below 65536), else 0; every element offset in the kernels is 64-bit.
+ * nbp_tlsc_workspace_bytes: the scratch `ws` of both entries (the fp32 column sums [B][_h][W][C] of the pool, reused
+ * for the attention map a [B][_h][_w][C] of the gate).
+ * nbp_tlsc_pool: V (fp32) from g (NHWC, `dtype` storage) by separable sliding sums accumulated in fp32: a vertical
+ * pass over k1 rows into ws, then a horizontal pass over k2 columns; O(1) loads per output (each walk restarts from a
+ * fresh window sum every <= 512 steps, which also bounds the running sum's rounding drift).
+ * nbp_tlsc_sca_gate: the SCA 1x1 conv per valid position (NAFNet_arch.py:39-41 on the local mean), a = wsca V + bsca in
+ * fp32 on v_mfma_f32_32x32x2_f32 into ws, then ga[p] = g[p] (.) a[clamp(p)] (:67), the product formed in fp32 and
+ * rounded once to g's storage type. */
+int nbp_tlsc_supported(int B, int H, int W, int C, int k1, int k2, int dtype);
+size_t nbp_tlsc_workspace_bytes(int B, int H, int W, int C, int k1, int k2);
+int nbp_tlsc_pool(const void* g, float* V, void* ws, int B, int H, int W, int C, int k1, int k2, int dtype,
+                  nbp_stream_t s);
+int nbp_tlsc_sca_gate(const void* g, const float* V, const float* wsca, const float* bsca, void* ga, void* ws, int B,
+                      int H, int W, int C, int k1, int k2, int dtype, nbp_stream_t s);
+
 /* SimpleGate on the FFN half (NAFNet_arch.py:75): g = t[:C]*t[C:], and its backward. */
 /* layout 0: t = [t_a | t_b] halves; layout 1: pairs (a_c, b_c) interleaved (the internal conv4 channel order). */
 int nbp_sg_fwd(const void* t, void* g, long M, int C, int layout, int dtype, nbp_stream_t s);

@@ -4,7 +4,7 @@ from __future__ import annotations
 import logging
 from typing import Any, Dict, Optional, Sequence
 
-from ..nafnet import NAFNet
+from ..nafnet import NAFNet, NAFNetLocal  # noqa: F401  (NAFNetLocal: the registry's full-resolution test-time variant)
 from .newbp_layer import CrosstalkPSF, build_psf_kernels
 
 logger = logging.getLogger(__name__)

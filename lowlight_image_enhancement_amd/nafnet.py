@@ -141,6 +141,8 @@ class NAFNet(nn.Module):
         # with level 0 / 1 alone
         self.c1dw_tile_channels = (32, 64)
         self._ln_carry = None
+        # {block prefix: TLSC kernel size}: set by NAFNetLocal only; None = every SCA pools globally
+        self._local_kernels: Optional[Dict[str, Tuple[int, int]]] = None
         # "fp32": fp32 operands everywhere (parity mode); "fp16" / "bf16": 16-bit activation storage and MFMA operands
         # with fp32 accumulation, statistics, parameters and gradients (fp16 = the reference's AMP autocast dtype,
         # image_restoration_model.py:255; the trainer adds GradScaler-style dynamic loss scaling for it).
@@ -477,24 +479,34 @@ class NAFNet(nn.Module):
                      c, bias=self._slice(P, pre + "conv1.bias"))
             call("dw_sg_pool_fwd", t1, self._slice(P, pre + "conv2.weight"), self._slice(P, pre + "conv2.bias"),
                  t2, g, pool, B, h, w, c, dt)
-        call("sca_fwd", pool, chunks, self._slice(P, pre + "sca.1.weight"), self._slice(P, pre + "sca.1.bias"),
-             mean, a, B, hw, c)
+        lk = self._local_window(pre, h, w)
+        if lk is None:
+            call("sca_fwd", pool, chunks, self._slice(P, pre + "sca.1.weight"), self._slice(P, pre + "sca.1.bias"),
+                 mean, a, B, hw, c)
+            gs, am, asc = g, AM_SCALE, a
+        else:
+            # TLSC local window (NAFNetLocal): the pool partials above are ignored; g (.) a is formed per pixel and
+            # conv3 and the rest of the block run on it with a unit scale
+            gs, am, asc = self._local_sca(P, pre, g, B, h, w, c, lk, tape), AM_PLAIN, None
+            if rows_ffn:
+                asc = torch.ones(B, c, device=dev)
+        arows = hw if lk is None else 1
         if rows_ffn:
             lnw, lnb = ((self._slice(P, next_pre + "norm1.weight"), self._slice(P, next_pre + "norm1.bias"))
                         if carry_next else (None, None))
-            call("ffn_rows_fwd", g, a, hw, x, self._slice(self._W[3], pre + "conv3.weight"),
+            call("ffn_rows_fwd", gs, asc, hw, x, self._slice(self._W[3], pre + "conv3.weight"),
                  self._slice(P, pre + "conv3.bias"), self._slice(P, pre + "beta"), self._slice(P, pre + "norm2.weight"),
                  self._slice(P, pre + "norm2.bias"), self._slice(self._W[3], pre + "conv4.weight"),
                  self._slice(P, pre + "conv4.bias"), self._slice(self._W[3], pre + "conv5.weight"),
                  self._slice(P, pre + "conv5.bias"), self._slice(P, pre + "gamma"), lnw, lnb, y, n2, st2, t4, g2, out,
                  nn1, nst1, M, c, LN_EPS, dt)
         elif fuse_ln:
-            call("gemm_res_ln", g, c, AM_SCALE, a, hw, self._slice(self._W[1], pre + "conv3.weight"), c, y,
+            call("gemm_res_ln", gs, c, am, asc, arows, self._slice(self._W[1], pre + "conv3.weight"), c, y,
                  M, c, c, self._slice(P, pre + "conv3.bias"), x, self._slice(P, pre + "beta"),
                  self._slice(P, pre + "norm2.weight"), self._slice(P, pre + "norm2.bias"), n2, st2, LN_EPS,
                  dt)
         else:
-            self._mm(self._W, g, c, AM_SCALE, a, hw, pre + "conv3.weight", y, c, CM_PLAIN, M, c, c,
+            self._mm(self._W, gs, c, am, asc, arows, pre + "conv3.weight", y, c, CM_PLAIN, M, c, c,
                      bias=self._slice(P, pre + "conv3.bias"), R=x, rscale=self._slice(P, pre + "beta"))
             call("ln_fwd_nhwc", y, self._slice(P, pre + "norm2.weight"), self._slice(P, pre + "norm2.bias"),
                  n2, st2, M, c, LN_EPS, dt)
@@ -539,6 +551,33 @@ class NAFNet(nn.Module):
         dt = self.dt
         return (self.fuse_c1dw_tile and c in self.c1dw_tile_channels and dt != 0
                 and query("c1dw_tile_supported", B, h, w, c, dt) == 1)
+
+    def _local_window(self, pre: str, h: int, w: int) -> Optional[Tuple[int, int]]:
+        """The TLSC window (k1, k2) of block `pre` on an h x w map, or None where the block pools globally: always in
+        the plain NAFNet, and in NAFNetLocal where the block's kernel covers the map (local_arch.py:42-43, 64)."""
+        if self._local_kernels is None:
+            return None
+        k = self._local_kernels[pre]
+        if k[0] >= h and k[1] >= w:
+            return None
+        return min(h, k[0]), min(w, k[1])
+
+    def _local_sca(self, P, pre, g, B, h, w, c, lk, tape):
+        """g (.) a with the per-pixel attention map of a local window: nbp_tlsc_pool -> nbp_tlsc_sca_gate."""
+        if tape is not None:
+            raise RuntimeError(f"NAFNetLocal is inference only: block {pre[:-1]} pools over a local {lk[0]} x {lk[1]} "
+                               f"window on its {h} x {w} map and has no backward (run under torch.no_grad())")
+        k1, k2 = lk
+        dt = self.dt
+        if query("tlsc_supported", B, h, w, c, k1, k2, dt) != 1:
+            raise _lib.NBPError(f"nbp_tlsc: shape not served (B {B}, {h} x {w} x {c}, window {k1} x {k2}, dtype {dt})")
+        V = torch.empty(B, h - k1 + 1, w - k2 + 1, c, device=g.device)
+        ws = torch.empty(query("tlsc_workspace_bytes", B, h, w, c, k1, k2), device=g.device, dtype=torch.uint8)
+        ga = torch.empty(B * h * w, c, device=g.device, dtype=self.adt)
+        call("tlsc_pool", g, V, ws, B, h, w, c, k1, k2, dt)
+        call("tlsc_sca_gate", g, V, self._slice(P, pre + "sca.1.weight"), self._slice(P, pre + "sca.1.bias"), ga, ws,
+             B, h, w, c, k1, k2, dt)
+        return ga
 
     def _down_fwd(self, P, i, x, B, h, w, c, tape):
         ho, wo = h // 2, w // 2
@@ -966,3 +1005,81 @@ class _NAFNetFn(torch.autograd.Function):
                                hook=net.grad_ready_hook)
         ctx.tape = None
         return dx, dflat, None
+
+
+def tlsc_kernel_sizes(train_size: Sequence[int], levels: int) -> List[Tuple[int, int]]:
+    """TLSC kernel size per U-Net level 0 .. levels (the middle), as the reference's conversion fixes them by one
+    forward at train_size (NAFNet_arch.py:169-174, local_arch.py:30-36): base = (int(1.5 Ht), int(1.5 Wt)), and a block
+    whose map at the padded train size is (ht, wt) gets (ht base[0] // Ht, wt base[1] // Wt)."""
+    Ht, Wt = int(train_size[-2]), int(train_size[-1])
+    base = (int(Ht * 1.5), int(Wt * 1.5))
+    ps = 2 ** levels
+    hp, wp = Ht + (ps - Ht % ps) % ps, Wt + (ps - Wt % ps) % ps
+    return [((hp >> lv) * base[0] // Ht, (wp >> lv) * base[1] // Wt) for lv in range(levels + 1)]
+
+
+class NAFNetLocal(NAFNet):
+    """NAFNetLocal(*args, train_size=(1, 3, 256, 256), fast_imp=False, **kwargs) (NAFNet_arch.py:164-174): NAFNet with
+    the test-time local converter (TLSC, local_arch.py:10-104) for inference on images larger than the training crops.
+    Every SCA whose kernel (1.5 x the block's map at train_size) does not cover its map pools over that sliding window
+    instead of the whole map (nbp_tlsc_pool / nbp_tlsc_sca_gate); blocks whose kernel covers the map take NAFNet's
+    global path unchanged.  Same state_dict keys as NAFNet.  Inference only: a forward that would record a backward
+    through a local block raises; an input on which every block is global behaves exactly as NAFNet."""
+
+    def __init__(self, *args, train_size=(1, 3, 256, 256), fast_imp=False, **kwargs):
+        if fast_imp:
+            raise NotImplementedError("NAFNetLocal: fast_imp=True (the reference's non-equivalent shortcut, "
+                                      "local_arch.py:45-59) is not implemented; use the exact path (fast_imp=False)")
+        super().__init__(*args, **kwargs)
+        self._set_train_size(train_size)
+
+    def _set_train_size(self, train_size):
+        self.train_size = tuple(int(v) for v in train_size)
+        L = len(self.enc_blk_nums)
+        ks = tlsc_kernel_sizes(self.train_size, L)
+        kern: Dict[str, Tuple[int, int]] = OrderedDict()
+        for i, n in enumerate(self.enc_blk_nums):
+            for j in range(n):
+                kern[f"encoders.{i}.{j}."] = ks[i]
+        for j in range(self.middle_blk_num):
+            kern[f"middle_blks.{j}."] = ks[L]
+        for i, n in enumerate(self.dec_blk_nums):
+            for j in range(n):
+                kern[f"decoders.{i}.{j}."] = ks[L - 1 - i]
+        self._local_kernels = kern
+
+    @property
+    def local_kernels(self) -> Dict[str, Tuple[int, int]]:
+        """{block prefix: (k[0], k[1])}, the reference's AvgPool2d.kernel_size of that block's SCA"""
+        return dict(self._local_kernels)
+
+    def local_blocks(self, H: int, W: int) -> Dict[str, bool]:
+        """{block prefix: whether the block pools locally} for an H x W input (local_arch.py:42)."""
+        hp, wp = self.check_image_size_hw(H, W)
+        L = len(self.enc_blk_nums)
+        out = OrderedDict()
+        for pre in self._local_kernels:
+            kind, i = pre.split(".")[0], int(pre.split(".")[1])
+            lv = i if kind == "encoders" else (L if kind == "middle_blks" else L - 1 - i)
+            out[pre] = self._local_window(pre, hp >> lv, wp >> lv) is not None
+        return out
+
+    @classmethod
+    def from_net(cls, net: NAFNet, train_size=(1, 3, 256, 256)) -> "NAFNetLocal":
+        """A local view of `net` for validation inside a training loop: it shares net.flat (the same Parameter, no
+        copy, so it follows the trainer's updates) and takes over net's precision and fusion switches."""
+        view = cls.__new__(cls)
+        view.__dict__.update(net.__dict__)  # shallow: _parameters is net's own dict, flat the same Parameter
+        view._ln_carry = None
+        view._keep = None
+        view._set_train_size(train_size)
+        return view
+
+    def forward(self, inp: torch.Tensor) -> torch.Tensor:
+        if inp.dim() == 4 and torch.is_grad_enabled() and (self.flat.requires_grad or inp.requires_grad):
+            loc = [p for p, v in self.local_blocks(inp.shape[2], inp.shape[3]).items() if v]
+            if loc:
+                raise RuntimeError(f"NAFNetLocal is inference only: {len(loc)} block(s) (first: {loc[0][:-1]}) pool over "
+                                   f"a local window for a {inp.shape[2]} x {inp.shape[3]} input and have no backward; "
+                                   "run under torch.no_grad()")
+        return super().forward(inp)
