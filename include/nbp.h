@@ -372,6 +372,30 @@ int nbp_tlsc_pool(const void* g, float* V, void* ws, int B, int H, int W, int C,
 int nbp_tlsc_sca_gate(const void* g, const float* V, const float* wsca, const float* bsca, void* ga, void* ws, int B,
                       int H, int W, int C, int k1, int k2, int dtype, nbp_stream_t s);
 
+/* Tiled full-frame inference: the validation loop's grids() / grids_inverse() (NAFNet_base/basicsr/models/
+ * image_restoration_model.py:167-245; scale 1).  The [C][H][W] frame is cut into overlapping crop_h x crop_w tiles, the
+ * network runs on the tiles, the overlapping outputs are averaged back.  Per axis (extent h, crop c): n = (h - 1) / c + 1
+ * tiles, step = c when n == 1, else ceil((h - c) / (n - 1) - 1e-8); tile k starts at k * step for k < n - 1 and at h - c
+ * for the last (h 97, c 24: 0, 19, 38, 57, 73).  Tiles are numbered row-major, t = r * n_cols + q: the reference's
+ * `idxes` order.  A pixel is covered by at most two tiles per axis.
+ * nbp_grid_plan: host only; the plan in integer arithmetic (equal to the reference's float expression for every int
+ * extent).  NBP_ERR_ARG when crop_h < 1, crop_w < 1, crop_h > H or crop_w > W (the reference then slices with a
+ * negative start).
+ * nbp_grid_gather: tiles t0 .. t0 + n - 1 of img as the batch [n][C][crop_h][crop_w] (:212, 218), bit copies.
+ * nbp_grid_blend: all T = n_rows * n_cols tile outputs [T][C][crop_h][crop_w] -> out [C][H][W] in one launch (:238-244):
+ * each pixel adds its covering tiles in ascending t onto +0.0f, one fp32 add at a time, and divides once by their number
+ * -- the reference's zeros / += per tile / divide by the count map, so out is bitwise equal to it.  No atomics, no
+ * workspace, every pixel written once.
+ * Both kernels take the plan nbp_grid_plan returns for (H, W, crop_h, crop_w) and refuse any other; they use 16-byte
+ * accesses where the rows they write are 16-byte aligned and, in the blend, every tile edge is a multiple of 4 (gather:
+ * crop_w a multiple of 4 and tiles aligned; blend: W, crop_w and step_j multiples of 4 and out aligned; the rows read
+ * may start at any 4-byte address); element offsets are 64-bit. */
+int nbp_grid_plan(int H, int W, int crop_h, int crop_w, int* n_rows, int* step_i, int* n_cols, int* step_j);
+int nbp_grid_gather(const float* img, float* tiles, int C, int H, int W, int crop_h, int crop_w, int n_rows, int step_i,
+                    int n_cols, int step_j, int t0, int n, nbp_stream_t s);
+int nbp_grid_blend(const float* tiles, float* out, int C, int H, int W, int crop_h, int crop_w, int n_rows, int step_i,
+                   int n_cols, int step_j, nbp_stream_t s);
+
 /* SimpleGate on the FFN half (NAFNet_arch.py:75): g = t[:C]*t[C:], and its backward. */
 /* layout 0: t = [t_a | t_b] halves; layout 1: pairs (a_c, b_c) interleaved (the internal conv4 channel order). */
 int nbp_sg_fwd(const void* t, void* g, long M, int C, int layout, int dtype, nbp_stream_t s);

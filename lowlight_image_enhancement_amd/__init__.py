@@ -13,13 +13,16 @@ so unmodified train/eval scripts import this implementation.
 import sys
 
 __version__ = "0.1.0"
-__all__ = ["NAFNet", "NAFNetLocal", "install_aliases"]
+__all__ = ["NAFNet", "NAFNetLocal", "grid_plan", "tiled_forward", "val_forward", "install_aliases"]
 
 
 def __getattr__(name):  # the networks, imported on first use (importing the package alone stays free of torch)
     if name in ("NAFNet", "NAFNetLocal"):
         from . import nafnet
         return getattr(nafnet, name)
+    if name in ("grid_plan", "tiled_forward", "val_forward"):  # tiled full-frame inference (val.grids)
+        from . import tiling
+        return getattr(tiling, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
