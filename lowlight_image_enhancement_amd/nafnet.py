@@ -18,7 +18,9 @@ tensors the backward needs in a tape.
 """
 from __future__ import annotations
 
+import contextlib
 import math
+import warnings
 from collections import OrderedDict
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -72,6 +74,43 @@ def _block_keys(pre: str, c: int):
 
 def _ceil_to(v, m):
     return (v + 3) // 4 * 4 if m == 4 else v
+
+
+PRECISIONS = ("fp32", "bf16", "fp16")
+
+
+def pick_precision(setting: str, autocast_on: bool, autocast_dtype, width: int) -> Tuple[str, bool]:
+    """(precision of one forward, whether to warn) from a NAFNet.precision setting and the ambient CUDA autocast state.
+    An explicit "fp32" / "fp16" / "bf16" is returned as it is: autocast is ignored (and `dt` raises for a 16-bit
+    setting on a width that is no multiple of 8).  "auto" follows the region as the reference's fp32 module does under
+    it (image_restoration_model.py:255-257): fp32 outside an enabled region, the region's dtype inside one; a width
+    that is no multiple of 8 (the reference runs any width under autocast, the 16-bit kernels need 16-byte channel
+    vectors) stays fp32 there, with the warning flag set."""
+    if setting in PRECISIONS:
+        return setting, False
+    if setting != "auto":
+        raise ValueError(f"NAFNet precision must be 'auto', 'fp32', 'bf16' or 'fp16', got {setting!r}")
+    if not autocast_on:
+        return "fp32", False
+    if autocast_dtype == torch.float16:
+        name = "fp16"
+    elif autocast_dtype == torch.bfloat16:
+        name = "bf16"
+    else:
+        raise ValueError(f"NAFNet under torch.autocast: dtype {autocast_dtype} has no 16-bit kernels (float16 or "
+                         "bfloat16)")
+    if width % 8:
+        return "fp32", True
+    return name, False
+
+
+class Tape(list):
+    """The executor's tape: the records of one forward plus the precision that forward ran in.  The backward runs in
+    the tape's precision whatever the module's setting or the autocast state is by then."""
+
+    def __init__(self, precision: str):
+        super().__init__()
+        self.precision = precision
 
 
 class NAFNet(nn.Module):
@@ -145,8 +184,14 @@ class NAFNet(nn.Module):
         self._local_kernels: Optional[Dict[str, Tuple[int, int]]] = None
         # "fp32": fp32 operands everywhere (parity mode); "fp16" / "bf16": 16-bit activation storage and MFMA operands
         # with fp32 accumulation, statistics, parameters and gradients (fp16 = the reference's AMP autocast dtype,
-        # image_restoration_model.py:255; the trainer adds GradScaler-style dynamic loss scaling for it).
-        self.precision = "fp32"
+        # image_restoration_model.py:255; the trainer adds GradScaler-style dynamic loss scaling for it).  "auto" (the
+        # default): resolved once per forward from the ambient CUDA autocast region (pick_precision), so the reference's
+        # AMP step selects the 16-bit kernels with no attribute of this module set.
+        self.precision = "auto"
+        # the precision of the forward / backward the executor is running (set by exec_forward / exec_backward for their
+        # duration; dt / adt read it): a backward runs in its tape's precision, not in a newly resolved one
+        self._active: Optional[str] = None
+        self._warned_width = False
         # 16-bit modes: the layer scales beta / gamma are folded into the transposed conv3 / conv5 weight copies (the
         # dgrad operands: dh = (beta (.) dy) W3 = dy (diag(beta) W3)), so those dgrads read A unscaled
         self.fold_ls = True
@@ -257,17 +302,48 @@ class NAFNet(nn.Module):
             call("frag16", wt, self._fdesc_t, self._fdesc_t.shape[0], wtf)
         return wb, wt, wf, wtf
 
+    def resolved_precision(self) -> str:
+        """The precision a forward started now would run in: the setting, or for "auto" what the ambient CUDA autocast
+        region selects (pick_precision)."""
+        name, warn = pick_precision(self.precision, torch.is_autocast_enabled("cuda"),
+                                    torch.get_autocast_dtype("cuda"), self.width)
+        if warn and not self._warned_width:
+            self._warned_width = True
+            warnings.warn(f"NAFNet(width={self.width}) under torch.autocast runs its fp32 kernels: the 16-bit modes need "
+                          "a width that is a multiple of 8 (16-byte vectors of 16-bit channels)", RuntimeWarning,
+                          stacklevel=2)
+        return name
+
+    @property
+    def active_precision(self) -> str:
+        """The pinned precision while the executor runs a forward or a backward, else resolved_precision()."""
+        return self._active if self._active is not None else self.resolved_precision()
+
+    @contextlib.contextmanager
+    def _pinned(self, precision: str):
+        """Run the executor in `precision`, out of reach of the ambient autocast region (as torch.amp.custom_fwd runs a
+        function's body): dt / adt read the pin, no torch op inside is re-typed."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"NAFNet executor precision must be 'fp32', 'bf16' or 'fp16', got {precision!r}")
+        prev, self._active = self._active, precision
+        try:
+            with torch.autocast("cuda", enabled=False):
+                yield
+        finally:
+            self._active = prev
+
     @property
     def adt(self) -> torch.dtype:
         """storage dtype of NHWC activations and activation gradients"""
-        return {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[self.precision]
+        return {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[self.active_precision]
 
     @property
     def dt(self) -> int:
         """dtype code of the C-ABI: 0 fp32, 1 bf16, 2 fp16"""
-        d = {"fp32": 0, "bf16": 1, "fp16": 2}[self.precision]
+        prec = self.active_precision
+        d = {"fp32": 0, "bf16": 1, "fp16": 2}[prec]
         if d and self.width % 8:
-            raise ValueError(f"precision {self.precision!r} needs a width that is a multiple of 8 (16-byte vectors of "
+            raise ValueError(f"precision {prec!r} needs a width that is a multiple of 8 (16-byte vectors of "
                              f"16-bit channels); width {self.width} runs in the fp32 mode")
         return d
 
@@ -381,12 +457,20 @@ class NAFNet(nn.Module):
         return out
 
     # The executor.  Every op appends a record to the tape when save=True.
-    def exec_forward(self, x: torch.Tensor, save: bool, flat: Optional[torch.Tensor] = None):
+    def exec_forward(self, x: torch.Tensor, save: bool, flat: Optional[torch.Tensor] = None,
+                     precision: Optional[str] = None):
+        """The forward.  `precision`: "fp32" / "fp16" / "bf16" to run in (a caller's own pin, NBPTrainer's); None: the
+        module's setting, "auto" resolved here, once, from the ambient autocast region.  The returned tape carries it."""
+        prec = self.resolved_precision() if precision is None else precision
+        with self._pinned(prec):
+            return self._forward_pinned(x, save, flat, prec)
+
+    def _forward_pinned(self, x, save, flat, prec):
         P = self.flat.data if flat is None else flat
         B, Ci, H0, W0 = x.shape
         Hp, Wp = self.check_image_size_hw(H0, W0)
-        tape: List[tuple] = []
-        Wt = (P,) if self.precision == "fp32" else (P,) + self._prep_weights(P)
+        tape = Tape(prec)
+        Wt = (P,) if prec == "fp32" else (P,) + self._prep_weights(P)
         self._W = Wt
         self._ln_carry = None
         w = self.width
@@ -602,18 +686,22 @@ class NAFNet(nn.Module):
     def exec_backward(self, tape, dout: torch.Tensor, dflat: torch.Tensor, need_dx: bool,
                       flat: Optional[torch.Tensor] = None, hook: Optional[Callable[[Stage], None]] = None):
         """Walk the tape in reverse.  Writes every parameter gradient (exactly once) into dflat, calls
-        hook(stage) as each stage's gradient slice is complete, returns d(input) or None."""
+        hook(stage) as each stage's gradient slice is complete, returns d(input) or None.  Runs in the precision the
+        tape's forward ran in (Tape.precision): the backward of an AMP step is called outside the autocast region
+        (image_restoration_model.py:306-310), and autograd's backward thread does not see the forward's region either."""
         P = self.flat.data if flat is None else flat
-        self._keep = []
-        call("grad_reduce_defer")
-        try:
-            return self._walk_backward(tape, dout, dflat, need_dx, P, hook)
-        finally:
-            if self._grouping:  # an error inside a grouped level: launch what is queued so the library state is reset
-                self._grouping = False
-                call("wgrad_group", 0)
-            call("grad_reduce_flush", 1)
-            self._keep = None
+        prec = getattr(tape, "precision", None)
+        with self._pinned(self.resolved_precision() if prec is None else prec):
+            self._keep = []
+            call("grad_reduce_defer")
+            try:
+                return self._walk_backward(tape, dout, dflat, need_dx, P, hook)
+            finally:
+                if self._grouping:  # an error inside a grouped level: launch what is queued so the library state is reset
+                    self._grouping = False
+                    call("wgrad_group", 0)
+                call("grad_reduce_flush", 1)
+                self._keep = None
 
     def _level_grouped(self, c: int) -> bool:
         return self.dt != 0 and c % 128 == 0 and self.group_wgrad
@@ -1067,11 +1155,13 @@ class NAFNetLocal(NAFNet):
     @classmethod
     def from_net(cls, net: NAFNet, train_size=(1, 3, 256, 256)) -> "NAFNetLocal":
         """A local view of `net` for validation inside a training loop: it shares net.flat (the same Parameter, no
-        copy, so it follows the trainer's updates) and takes over net's precision and fusion switches."""
+        copy, so it follows the trainer's updates) and takes over net's precision setting ("auto" stays "auto": each
+        forward of the view resolves it anew, nothing is cached) and fusion switches."""
         view = cls.__new__(cls)
         view.__dict__.update(net.__dict__)  # shallow: _parameters is net's own dict, flat the same Parameter
         view._ln_carry = None
         view._keep = None
+        view._active = None
         view._set_train_size(train_size)
         return view
 

@@ -58,8 +58,13 @@ class NBPTrainer:
         SSIM, Phys_srgb; a zero weight skips the term.  `perceptual` / `lpips`: PerceptualLoss / LPIPS modules
         (constructed with the synthetic offline weights when needed and not given; `lpips_net` picks the backbone of
         a constructed LPIPS: 'vgg' as HybridLossPlus, or 'alex' as BASELINE.json cfg3 names it).  `loss_scale`: "auto" (dynamic
-        GradScaler scaling when net.precision == "fp16"), "dynamic" or None; the GradScaler arguments are torch's
-        defaults.  A step whose gradient is non-finite leaves parameters and moments untouched in every mode."""
+        GradScaler scaling when the network runs in fp16), "dynamic" or None; the GradScaler arguments are torch's
+        defaults.  A step whose gradient is non-finite leaves parameters and moments untouched in every mode.
+
+        A net left at precision "auto" is resolved here, once (NAFNet.resolved_precision: fp32 outside a CUDA autocast
+        region, the region's dtype when the trainer is built inside one); the loss scaler and the VGG / LPIPS trunk type
+        follow that value, and every step runs the executor in it whatever region the caller is in by then.  An explicit
+        net.precision is read at every step, as before."""
         self.net = net
         dev = net.flat.device
         self.dev = dev
@@ -97,15 +102,16 @@ class NBPTrainer:
         self._lr_dev = torch.zeros(1, device=dev)
         # GradScaler (image_restoration_model.py:104-106, torch.cuda.amp defaults): dynamic loss scaling whenever the
         # activations are stored in fp16 (the reference's autocast dtype); fp32 / bf16 need none (8-bit exponent)
+        self.precision = prec = net.resolved_precision()
         if loss_scale == "auto":
-            loss_scale = "dynamic" if net.precision == "fp16" else None
+            loss_scale = "dynamic" if prec == "fp16" else None
         self.scaler = (torch.tensor([init_scale, growth_factor, backoff_factor, float(growth_interval)],
                                     dtype=torch.float32, device=dev) if loss_scale == "dynamic" else None)
         # VGG / LPIPS trunk type for modules left at precision "auto" (the trainer's default ones): fp32 in the fp32
         # parity mode (the reference's fp32 trunk); in the 16-bit modes the autocast counterpart -- fp16 only under a
         # loss scale (its ~1/n feature gradients underflow fp16 otherwise), else bf16.  A module given an explicit
         # precision keeps it; the trainer never changes a module's attributes.
-        self.vgg_dt = 0 if net.precision == "fp32" else (2 if net.precision == "fp16" and self.scaler is not None else 1)
+        self.vgg_dt = 0 if prec == "fp32" else (2 if prec == "fp16" and self.scaler is not None else 1)
         self.loss_buf = torch.zeros(6, device=dev)  # L1, SSIM, Phys, DeltaE, Perc, Total
         self.iter = 0  # iterations run (the scheduler's position; AdamW's own step count self.t excludes skips)
         self.pg = process_group
@@ -197,7 +203,8 @@ class NBPTrainer:
         lq, gt = lq.contiguous(), gt.contiguous()
         B, C, H, W = lq.shape
         self._ensure_up(B)
-        out, tape = net.exec_forward(lq, save=True)
+        # an "auto" net runs in the precision pinned at construction; the backward follows the tape
+        out, tape = net.exec_forward(lq, save=True, precision=self.precision if net.precision == "auto" else None)
         n = out.numel()
         wl1, wss, wph = self.w
         d_out = torch.empty_like(out)
