@@ -591,6 +591,14 @@ int nbp_png_decode_batch(int n, const void* const* bufs, const long* lens, const
  * short/65535, long_raw (= gt = long) = long/65535, NCHW float32 [B][3][H][W] (sony_sid_lmdb_dataset.py:207-218). */
 int nbp_sid_to_float(const void* short_u16, const void* long_u16, const float* ratio, int B, int H, int W, float* lq,
                      float* short_raw, float* long_raw, nbp_stream_t s);
+/* Device, HBM-resident dataset: the same three outputs cut out of whole frames that live on the device.  frames is a
+ * device array [F] of device pointers to uint16 HWC RGB frames, frame_hw a device int [F][2] of their rows and
+ * columns (frames may differ in size), desc a device int [B][4] = short frame, long frame, top, left, ratio a device
+ * float [B]; output pixel (y, x) of sample b reads pixel (top + y, left + x) of both named frames.  The h x w window
+ * is common to the batch (whole frames and B up to 65535 are fine).  The caller validates the descriptors; the
+ * kernel also clamps the frame index to [0, F) and the source pixel to the frame, so it never reads outside one. */
+int nbp_sid_crop_to_float(const void* const* frames, const int* frame_hw, const int* desc, const float* ratio, int B,
+                          int F, int h, int w, float* lq, float* short_raw, float* long_raw, nbp_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,8 @@ import numpy as np
 import torch
 from torch.utils.data.sampler import Sampler
 
+from .sony_sid_resident_dataset import SonySIDResidentDataset
+
 
 class EnlargedSampler(Sampler):
     """EnlargedSampler(dataset, num_replicas, rank, ratio=1): rank's strided share of torch.randperm(total_size)
@@ -53,7 +55,11 @@ def create_dataloader(dataset, dataset_opt, num_gpu=1, dist=False, sampler=None,
     """basicsr create_dataloader: train -> batch_size_per_gpu (x num_gpu when not distributed), drop_last, shuffle
     unless a sampler is given, persistent workers when num_workers > 0; val / test -> batch 1.  prefetch_mode
     None / 'cuda' give a DataLoader whose batches CUDAPrefetcher converts on the GPU; 'cpu' (the reference's
-    CPUPrefetcher of float tensors) is not offered, the float conversion being a device kernel here."""
+    CPUPrefetcher of float tensors) is not offered, the float conversion being a device kernel here.
+
+    A SonySIDResidentDataset is always loaded with num_workers=0, whatever num_worker_per_gpu says: an item is a
+    few RNG draws and a descriptor (the pixels never leave the device), so workers have nothing to parallelise, and
+    one process keeps the order of the crop draws equal to the sampler's order."""
     phase = dataset_opt["phase"]
     if rank is None:
         rank = torch.distributed.get_rank() if torch.distributed.is_available() and \
@@ -66,6 +72,8 @@ def create_dataloader(dataset, dataset_opt, num_gpu=1, dist=False, sampler=None,
             multiplier = 1 if num_gpu == 0 else num_gpu
             batch_size = dataset_opt["batch_size_per_gpu"] * multiplier
             num_workers = dataset_opt["num_worker_per_gpu"] * multiplier
+        if isinstance(dataset, SonySIDResidentDataset):
+            num_workers = 0
         args = dict(dataset=dataset, batch_size=batch_size, shuffle=sampler is None, num_workers=num_workers,
                     sampler=sampler, drop_last=True, persistent_workers=num_workers > 0)
         args["worker_init_fn"] = partial(worker_init_fn, num_workers=num_workers, rank=rank, seed=seed) \

@@ -6,6 +6,10 @@ current stream wait for it.  The batches of SonySIDLMDBDataset carry the uint16 
 after the upload, ``nbp_sid_to_float`` (sid.hip) turns them into the reference's float32 NCHW tensors, so the step
 receives the reference's batch dict.  Aliasing as in the reference: ``short`` and ``short_obs`` are ``lq``; ``long``
 is ``gt``; ``long_raw`` has the values of ``gt`` (the same tensor here).
+
+The batches of SonySIDResidentDataset carry crop descriptors and no pixels (no ``lq_u16`` key): the frames already
+live on the device, and the dataset's ``crop_batch`` (sid_resident.hip) writes the same three tensors.  The
+prefetcher finds the dataset as ``loader.dataset``.
 """
 from __future__ import annotations
 
@@ -16,9 +20,12 @@ import torch
 from .._lib import call
 
 
-def to_reference_batch(batch: Dict, device: torch.device) -> Dict:
+def to_reference_batch(batch: Dict, device: torch.device, dataset=None) -> Dict:
     """Device batch dict from a collated uint16 batch, enqueued on the current stream (tensors moved with
-    non_blocking=True: pinned host memory gives an asynchronous copy)."""
+    non_blocking=True: pinned host memory gives an asynchronous copy).  A collated descriptor batch (``desc``, no
+    ``lq_u16``) is cut out of the resident frames by ``dataset.crop_batch`` instead; the dict is the same."""
+    if "lq_u16" not in batch:
+        return _resident_batch(batch, device, dataset)
     out = {}
     for k, v in batch.items():
         if k in ("lq_u16", "gt_u16"):
@@ -34,6 +41,18 @@ def to_reference_batch(batch: Dict, device: torch.device) -> Dict:
     short_raw = torch.empty_like(lq)
     gt = torch.empty_like(lq)
     call("sid_to_float", s16, l16, ratio, B, H, W, lq, short_raw, gt)
+    out.update({"lq": lq, "gt": gt, "short": lq, "long": gt, "short_raw": short_raw, "long_raw": gt,
+                "short_obs": lq})
+    return out
+
+
+def _resident_batch(batch: Dict, device: torch.device, dataset) -> Dict:
+    if "desc" not in batch or not hasattr(dataset, "crop_batch"):
+        raise ValueError("expected a uint16 batch (lq_u16 / gt_u16) or a descriptor batch (desc) together with the "
+                         "resident dataset that made it")
+    out = {k: (v.to(device=device, non_blocking=True) if torch.is_tensor(v) else v)
+           for k, v in batch.items() if k != "desc"}
+    lq, short_raw, gt = dataset.crop_batch(batch["desc"], out["expo_ratio"])
     out.update({"lq": lq, "gt": gt, "short": lq, "long": gt, "short_raw": short_raw, "long_raw": gt,
                 "short_obs": lq})
     return out
@@ -59,7 +78,7 @@ class CUDAPrefetcher:
             self.batch = None
             return
         with torch.cuda.stream(self.stream):
-            self.batch = to_reference_batch(raw, self.device)
+            self.batch = to_reference_batch(raw, self.device, getattr(self.ori_loader, "dataset", None))
 
     def next(self) -> Optional[Dict]:
         cur = torch.cuda.current_stream()
