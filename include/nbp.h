@@ -489,6 +489,27 @@ int nbp_ssim_linear(const float* pred, const float* tgt, int N, int C, int H, in
 /* |Sobel| of channel 0 of lab [B][3][H][W] (zero padding, +1e-12 under the root; color_error.py:296-302). */
 int nbp_sobel_mag(const float* lab, int B, int H, int W, float* out, nbp_stream_t s);
 
+/* ------------------------------------------------------------------ validation-pass statistics (valstats.hip) */
+/* Exact order statistics per row by radix select: x [rows][n] fp32 (1 <= n < 2^31, rows <= 65535), ranks
+   0 <= k_lo <= k_hi < n (zero-based, ascending order, the same for every row) -> out [rows][2] = the k_lo-th and the
+   k_hi-th smallest value of each row.  A row holding a NaN yields NaN in both slots.  Three reads of x (11 / 11 / 10
+   key bits), no sort, no host synchronisation.  ws: nbp_quantile_workspace_bytes(rows) bytes (cleared by the call). */
+size_t nbp_quantile_workspace_bytes(int rows);
+int nbp_quantile_select(const float* x, int rows, long n, long k_lo, long k_hi, void* ws, float* out, nbp_stream_t s);
+/* One pass over pred and tgt [B][3][H][W] sRGB (clamp != 0: both clamped to [0, 1] first): de [B][H][W] = the
+   metric-form CIEDE2000 (as nbp_de00_metric_map), grad [B][H][W] = |Sobel| of pred's L (as nbp_rgb_to_lab +
+   nbp_sobel_mag: zero padding of L, +1e-12 under the root) and de_mean [B] = the float64 mean of each image's de.
+   ws: nbp_val_color_workspace_doubles(B, H, W) doubles. */
+size_t nbp_val_color_workspace_doubles(int B, int H, int W);
+int nbp_val_color_maps(const float* pred, const float* tgt, int B, int H, int W, int clamp, float kL, float kC, float kH,
+                       float eps, double* ws, float* de, float* grad, double* de_mean, nbp_stream_t s);
+/* Masked reduction: over val, key [rows][n] fp32 and thr [rows] fp32 (device), sum [rows] float64 and count [rows]
+   int64 of val where key >= thr[row], and the same pooled over all rows (pooled_sum [1], pooled_count [1]).
+   Fixed-order.  ws: nbp_masked_mean_workspace_doubles(rows, n) doubles. */
+size_t nbp_masked_mean_workspace_doubles(int rows, long n);
+int nbp_masked_mean(const float* val, const float* key, const float* thr, int rows, long n, double* ws, double* sum,
+                    long long* count, double* pooled_sum, long long* pooled_count, nbp_stream_t s);
+
 /* ------------------------------------------------------------------ VGG feature losses (rows 19, 22) */
 /* 3x3 zero-padded conv over NHWC bf16 as an implicit GEMM on bf16 MFMA (K = 9*Cin gathered on the fly):
    y = epi(sum_{t,c} x[i + t/3 - 1][j + t%3 - 1][c] * w[n][t][c]); mode 0 = + bias then ReLU, 1 = + bias,

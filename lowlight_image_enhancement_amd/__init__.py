@@ -13,7 +13,7 @@ so unmodified train/eval scripts import this implementation.
 import sys
 
 __version__ = "0.1.0"
-__all__ = ["NAFNet", "NAFNetLocal", "grid_plan", "tiled_forward", "val_forward", "install_aliases"]
+__all__ = ["NAFNet", "NAFNetLocal", "grid_plan", "tiled_forward", "val_forward", "Validator", "install_aliases"]
 
 
 def __getattr__(name):  # the networks, imported on first use (importing the package alone stays free of torch)
@@ -23,6 +23,9 @@ def __getattr__(name):  # the networks, imported on first use (importing the pac
     if name in ("grid_plan", "tiled_forward", "val_forward"):  # tiled full-frame inference (val.grids)
         from . import tiling
         return getattr(tiling, name)
+    if name == "Validator":  # the device-resident validation pass (opt['val'])
+        from . import validation
+        return validation.Validator
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
