@@ -14,16 +14,21 @@ arch_util.py:264-300 (LayerNorm2d).  Same constructor signature, same state_dict
   sub-position (r1, r2, c').  state_dict()/load_state_dict() convert to and from the reference layout.
 
 The forward/backward executor launches the kernels of include/nbp.h on the current stream and keeps the
-tensors the backward needs in a tape.
+tensors the backward needs in a tape.  Which kernels a NAFBlock takes is decided in one place, once per block and
+forward (NAFNet._plan_block -> BlockPlan, from the precision, the fusion switches and the library's support
+queries); the plan is stored in the block's tape record and the backward follows it.  What one run carries between
+its launches (the weight copies, the LayerNorm carry, the tensors a deferred launch still reads) is a _Run object
+that the executor methods pass along; the module holds no per-run state but the pinned precision.
 """
 from __future__ import annotations
 
 import contextlib
 import math
+import os
 import warnings
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -36,12 +41,9 @@ CM_SG, CM_SGBWD = 4, 5  # SimpleGate forward / backward fused into the GEMM epil
 CM_CHANDOT = 8  # dgrad with the SCA channel-dot partials in the epilogue (bf16 mode, C > 64)
 CM_PLAIN, CM_D2S = 0, 1
 LN_EPS = 1e-6
-# without a gradient-ready hook (one process: no bucketed all-reduce reads a stage's slice early) every deferred
-# gradient reduction of the backward runs in the backward's final flush instead of one flush launch per stage: 26
-# latency-bound reduce launches per step become a few full ones (+1.0 % at cfg2, fp16, in the quick bench: 1356 / 1358
-# vs 1342 / 1344 img/s, gpurun_out r6c; the round-1 measurement of the same change was neutral).  NBP_LATE_FLUSH=0:
-# per-stage flushes (A/B)
-_LATE_FLUSH = __import__("os").environ.get("NBP_LATE_FLUSH", "1") != "0"
+# csrc/c1dw_tile.hip's A/B variants of nbp_c1dw_bwd_tile (read there): with either set the tile backward has no
+# SCA-folding form, so the executor launches the SCA backward on its own
+C1DW_BWD_VARIANT = bool(os.environ.get("NBP_C1DW_BWD_TH") or os.environ.get("NBP_C1DW_BWD_BAL"))
 
 
 @dataclass
@@ -72,8 +74,8 @@ def _block_keys(pre: str, c: int):
             (pre + "norm2.weight", (c,)), (pre + "norm2.bias", (c,))]
 
 
-def _ceil_to(v, m):
-    return (v + 3) // 4 * 4 if m == 4 else v
+def _ceil4(v):
+    return (v + 3) // 4 * 4
 
 
 PRECISIONS = ("fp32", "bf16", "fp16")
@@ -113,6 +115,48 @@ class Tape(list):
         self.precision = precision
 
 
+class Weights(NamedTuple):
+    """The parameters as one run's kernels read them.  fp32 runs carry f32 alone."""
+    f32: torch.Tensor  # the flat parameters
+    h: Optional[torch.Tensor] = None  # 16-bit copy
+    ht: Optional[torch.Tensor] = None  # 16-bit copy, GEMM weights transposed (the dgrad operands; layer scales folded in)
+    frag: Optional[torch.Tensor] = None  # fragment-ordered copy of h (nbp_ffn_rows_fwd), None when no level takes it
+    frag_t: Optional[torch.Tensor] = None  # fragment-ordered copy of ht (nbp_ffn_rows_bwd)
+
+
+@dataclass(frozen=True)
+class BlockPlan:
+    """The kernel path of one NAFBlock, decided once by NAFNet._plan_block in the forward and recorded in the block's
+    tape record: the backward obeys it and reads no switch, query or saved-tensor presence again."""
+    tile: bool  # conv1 -> depthwise -> SimpleGate -> pool on the tile path: t1 / t2 never stored, rebuilt in the backward
+    c1dw: bool  # the same chain as one whole-image launch (nbp_c1_dw_sg_pool), t1 / t2 stored
+    chunks: int  # pool partials per image
+    ln_epilogue: bool  # 16-bit at a width whose GEMM epilogues hold a LayerNorm (forward if ln_fwd; backward always)
+    ln_fwd: bool  # norm2 in conv3's epilogue, the next block's norm1 in conv5's
+    drop_t4: bool  # t4 not stored (level 0): the backward rebuilds it (nbp_dgrad_sg_rc*)
+    ffn: bool  # conv4 -> SimpleGate -> conv5 as nbp_gemm_ffn, g2 not stored either
+    rows_ffn: bool  # the FFN half, forward and backward, as the row-stationary launches (nbp_ffn_rows_fwd / _bwd)
+    local: Optional[Tuple[int, int]]  # the TLSC window, None: the SCA pools globally
+    carry_next: bool  # this block's last launch also makes the next block's norm1
+    # backward only
+    sg_rc_wg: bool  # with drop_t4: U5 / V5 and conv4's weight gradients folded into the rebuild pass
+    ln_wg: bool  # conv1's weight gradients folded into the conv1 dgrad + norm1 backward (level 0)
+    sca_fold: bool  # the SCA backward inside the depthwise backward
+    grouped: bool  # the wide weight gradients join the level's grouped launch
+    chandot: bool  # the SCA channel dot in conv3's dgrad epilogue
+    rows_pre: bool  # the conv1 input gradient may be deferred into the preceding block's nbp_ffn_rows_bwd
+
+
+@dataclass
+class _Run:
+    """What one exec_forward or one exec_backward carries from launch to launch."""
+    w: Weights
+    tape: Optional[Tape] = None  # forward: where the records go, None without a backward
+    ln_carry: Optional[tuple] = None  # forward: (x, n1, st1) a block's epilogue made for the next block
+    keep: List[torch.Tensor] = field(default_factory=list)  # backward: tensors awaiting a deferred launch / reduction
+    grouping: bool = False  # backward: inside a level whose weight gradients are queued (nbp_wgrad_group open)
+
+
 class NAFNet(nn.Module):
     """NAFNet(img_channel=3, width=16, middle_blk_num=1, enc_blk_nums=[], dec_blk_nums=[]) (NAFNet_arch.py:85)."""
 
@@ -135,17 +179,15 @@ class NAFNet(nn.Module):
         self.flat = nn.Parameter(torch.zeros(self.numel, dtype=torch.float32))
         self._init_reference_like()
         self.grad_ready_hook: Optional[Callable[[Stage], None]] = None
-        self._keep: Optional[List[torch.Tensor]] = None  # slabs awaiting a deferred gradient reduction
-        # Fused / folded forms of the executor, all on (each measured faster; the environment knobs that
-        # toggled them for A/B runs were removed in round 4).  The attributes stay so that the GPU tests can compare
-        # a fused form bit for bit with its unfused one on the same network.
+        # Fused / folded forms of the executor, all on (each measured faster; no environment knob toggles
+        # them).  The attributes stay so that the GPU tests can compare a fused form bit for bit with its unfused one
+        # on the same network.  _plan_block reads them once per block in the forward; a backward follows its tape.
         # LayerNorm forward in the conv3 / conv5 epilogues at C in {32, 64, 128, 256}
         self.fuse_ln_fwd = True
         # the wide (C >= 128) weight gradients of a whole U-Net level (conv5's U, conv4, conv3's U, conv1 of every
         # NAFBlock of the level) queued during the level's backward and launched as ONE grouped launch at its end,
         # with M-splits chosen for the group (False: one launch per weight gradient)
         self.group_wgrad = True
-        self._grouping = False
         # level 0 (C = 32): the conv4 output t4 is not stored; the conv5 dgrad rebuilds it per tile on MFMA
         # (nbp_dgrad_sg_rc, bitwise equal) ...
         self.sg_rc = True
@@ -159,11 +201,11 @@ class NAFNet(nn.Module):
         # in one row-stationary launch (nbp_ffn_rows_fwd; bitwise the launches it replaces)
         self.fuse_ffn_rows = True
         # backward at those levels: a block's conv1 input gradient + norm1 backward deferred into the preceding block's
-        # row-stationary launch (nbp_ffn_rows_bwd with dt1: its dx made in LDS as that block's dout; NBP_FFN_PRE=0 off)
-        self.ffn_rows_pre = __import__("os").environ.get("NBP_FFN_PRE", "1") != "0"
-        # levels with the stored tape: the SCA backward (ds, the SCA weight gradients) inside the fused depthwise
-        # backward (nbp_sca_dw_bwd) instead of its own launch before it (NBP_SCA_FOLD=0: two launches)
-        self.sca_fold = __import__("os").environ.get("NBP_SCA_FOLD", "1") != "0"
+        # row-stationary launch (nbp_ffn_rows_bwd with dt1: its dx made in LDS as that block's dout)
+        self.ffn_rows_pre = True
+        # the SCA backward (ds, the SCA weight gradients) inside the fused depthwise backward (nbp_sca_dw_bwd, on the tile
+        # path nbp_sca_c1dw_bwd_tile) instead of its own launch before it
+        self.sca_fold = True
         # level 0: conv1's weight / bias gradients folded into the conv1 dgrad + norm1 backward pass (nbp_dgrad_ln_bwd_wg:
         # n1 rebuilt from x and the LN statistics, dt1 already in registers; False: a separate nbp_wgrad_f32 launch)
         self.ln_wg = True
@@ -179,7 +221,6 @@ class NAFNet(nn.Module):
         # forward's saved tape traffic repays (58 vs 109 us, 49 vs 57): graph step +1.1 % with both levels, +0.7 / +0.3 %
         # with level 0 / 1 alone
         self.c1dw_tile_channels = (32, 64)
-        self._ln_carry = None
         # {block prefix: TLSC kernel size}: set by NAFNetLocal only; None = every SCA pools globally
         self._local_kernels: Optional[Dict[str, Tuple[int, int]]] = None
         # "fp32": fp32 operands everywhere (parity mode); "fp16" / "bf16": 16-bit activation storage and MFMA operands
@@ -192,13 +233,10 @@ class NAFNet(nn.Module):
         # duration; dt / adt read it): a backward runs in its tape's precision, not in a newly resolved one
         self._active: Optional[str] = None
         self._warned_width = False
+
         # 16-bit modes: the layer scales beta / gamma are folded into the transposed conv3 / conv5 weight copies (the
         # dgrad operands: dh = (beta (.) dy) W3 = dy (diag(beta) W3)), so those dgrads read A unscaled
-        self.fold_ls = True
-
         def _scale_off(k):
-            if not self.fold_ls:
-                return -1
             for wk, sk in (("conv3.weight", "beta"), ("conv5.weight", "gamma")):
                 if k.endswith(wk):
                     return self.entries[k[:-len(wk)] + sk].offset
@@ -275,7 +313,7 @@ class NAFNet(nn.Module):
                 kind = "down" if k.startswith("downs.") and k.endswith("weight") else (
                     "up" if k.startswith("ups.") else ("sg" if ".conv4." in k else "plain"))
                 self.entries[k] = PEntry(k, shp, off, n, kind)
-                off += n if k == "ending.bias" else _ceil_to(n, 4)  # 16-byte aligned slices for float4 access
+                off += n if k == "ending.bias" else _ceil4(n)  # 16-byte aligned slices for float4 access
             self.stages[gname] = Stage(gname, lo, off)
         self.numel = off
 
@@ -284,9 +322,12 @@ class NAFNet(nn.Module):
         return k.endswith(("conv1.weight", "conv3.weight", "conv4.weight", "conv5.weight")) or (
             k.startswith(("downs.", "ups.")) and k.endswith("weight"))
 
-    def _prep_weights(self, P: torch.Tensor):
-        """16-bit copy of the flat parameters + transposed copies of the GEMM weights (for the dgrads) + fragment-ordered
-        copies of the deep levels' conv3 / conv4 / conv5 weights (nbp_ffn_rows_fwd; None when no level takes it)."""
+    def _prep_weights(self, P: torch.Tensor) -> Weights:
+        """The weight set of one run: P alone in fp32; else + its 16-bit copy + transposed copies of the GEMM weights (for
+        the dgrads) + fragment-ordered copies of the deep levels' conv3 / conv4 / conv5 weights (nbp_ffn_rows_fwd; None
+        when no level takes it)."""
+        if self.dt == 0:
+            return Weights(P)
         if self._tdesc is None or self._tdesc.device != P.device:
             self._tdesc = self._tdesc_cpu.to(P.device)
             self._fdesc = self._fdesc_cpu.to(P.device) if self._fdesc_cpu.shape[0] else None
@@ -300,7 +341,7 @@ class NAFNet(nn.Module):
             call("frag16", wb, self._fdesc, self._fdesc.shape[0], wf)
             wtf = torch.empty(self.numel, dtype=self.adt, device=P.device)
             call("frag16", wt, self._fdesc_t, self._fdesc_t.shape[0], wtf)
-        return wb, wt, wf, wtf
+        return Weights(P, wb, wt, wf, wtf)
 
     def resolved_precision(self) -> str:
         """The precision a forward started now would run in: the setting, or for "auto" what the ambient CUDA autocast
@@ -349,15 +390,16 @@ class NAFNet(nn.Module):
 
     def _mm(self, W, A, lda, amode, ascale, rows, wkey, C, ldc, cmode, M, N, K, gh=0, gw=0, cs=0, bias=None,
             R=None, rscale=None, pre=None, dgrad=False):
-        """One GEMM launch.  W = (fp32 flat,) or (fp32 flat, bf16 copy, bf16 transposed copy).
+        """One GEMM launch in the run's precision, W its Weights.
         forward: C[M,N] = A[M,K] . W[N,K]^T ; dgrad: C[M,N] = A[M,K] . W[K,N] (W stored [out=K][in=N])."""
-        if len(W) == 1:
-            Wf = self._slice(W[0], wkey)
+        dt = self.dt
+        if dt == 0:
+            Wf = self._slice(W.f32, wkey)
             call("gemm_f32", A, lda, amode, ascale, rows, Wf, N if dgrad else K, 0 if dgrad else 1, C, ldc, cmode,
                  M, N, K, gh, gw, cs, bias, R, rscale, pre)
         else:
-            Wb = self._slice(W[2] if dgrad else W[1], wkey)
-            call("gemm_bf16", A, lda, amode, ascale, rows, self.dt, Wb, K, C, ldc, cmode, self.dt, M, N, K, gh, gw, cs,
+            Wb = self._slice(W.ht if dgrad else W.h, wkey)
+            call("gemm_bf16", A, lda, amode, ascale, rows, dt, Wb, K, C, ldc, cmode, dt, M, N, K, gh, gw, cs,
                  bias, R, rscale, pre)
 
     # reference layout <-> internal layout
@@ -470,9 +512,7 @@ class NAFNet(nn.Module):
         B, Ci, H0, W0 = x.shape
         Hp, Wp = self.check_image_size_hw(H0, W0)
         tape = Tape(prec)
-        Wt = (P,) if prec == "fp32" else (P,) + self._prep_weights(P)
-        self._W = Wt
-        self._ln_carry = None
+        run = _Run(self._prep_weights(P), tape if save else None)
         w = self.width
         feat = torch.empty(B, Hp, Wp, w, device=x.device, dtype=self.adt)
         call("intro_fwd", x, self._slice(P, "intro.weight"), self._slice(P, "intro.bias"), feat, B, Ci, H0, W0, Hp,
@@ -485,147 +525,159 @@ class NAFNet(nn.Module):
             c = self.enc_chans[i]
             for j in range(n):
                 nxt = f"encoders.{i}.{j + 1}." if j + 1 < n else None
-                feat = self._block_fwd(P, f"encoders.{i}.{j}.", feat, B, h, wd, c, tape if save else None, nxt)
+                feat = self._block_fwd(P, f"encoders.{i}.{j}.", feat, B, h, wd, c, run, nxt)
             skips.append(feat)
-            feat = self._down_fwd(P, i, feat, B, h, wd, c, tape if save else None)
+            feat = self._down_fwd(P, i, feat, B, h, wd, c, run)
             h, wd = h // 2, wd // 2
         for j in range(self.middle_blk_num):
             nxt = f"middle_blks.{j + 1}." if j + 1 < self.middle_blk_num else None
-            feat = self._block_fwd(P, f"middle_blks.{j}.", feat, B, h, wd, self.mid_chan, tape if save else None, nxt)
+            feat = self._block_fwd(P, f"middle_blks.{j}.", feat, B, h, wd, self.mid_chan, run, nxt)
         for i, n in enumerate(self.dec_blk_nums):
             chan = self.dec_chans[i] * 2
-            feat = self._up_fwd(P, i, feat, skips[::-1][i], B, h, wd, chan, tape if save else None)
+            feat = self._up_fwd(P, i, feat, skips[::-1][i], B, h, wd, chan, run)
             h, wd = h * 2, wd * 2
             c = self.dec_chans[i]
             for j in range(n):
                 nxt = f"decoders.{i}.{j + 1}." if j + 1 < n else None
-                feat = self._block_fwd(P, f"decoders.{i}.{j}.", feat, B, h, wd, c, tape if save else None, nxt)
+                feat = self._block_fwd(P, f"decoders.{i}.{j}.", feat, B, h, wd, c, run, nxt)
         out = torch.empty(B, Ci, H0, W0, device=x.device)
         call("ending_fwd", feat, self._slice(P, "ending.weight"), self._slice(P, "ending.bias"), x, out, B, Ci, H0,
              W0, Hp, Wp, w, self.dt)
         if save:
             tape.append(("ending", feat, (B, Ci, H0, W0, Hp, Wp, w)))
-            tape.append(("weights", Wt))
-        self._W = None
+            tape.append(("weights", run.w))
         return out, tape
 
-    def _block_fwd(self, P, pre, x, B, h, w, c, tape, next_pre=None):
-        """One NAFBlock forward (NAFNet_arch.py:60-80).  At C in {32, 64, 128} (bf16) the LayerNorms run in the epilogue
-        of the GEMM producing their input (nbp_gemm_res_ln): norm2 in conv3's, the next block's norm1 (next_pre)
-        in conv5's; that block then takes (n1, st1) from self._ln_carry."""
+    def _plan_block(self, W: Weights, B, h, w, c, pre, next_pre, save) -> BlockPlan:
+        """Every path decision of one NAFBlock, forward and backward: the one place where the switches and the
+        library's support queries are read for it."""
+        dt = self.dt
+        M, hw = B * h * w, h * w
+        ln_epilogue = dt != 0 and c in (32, 64, 128, 256)
+        ln_fwd = self.fuse_ln_fwd and ln_epilogue
+        tile = self.tile_level(B, h, w, c)
+        c1dw = not tile and self.fuse_c1dw and dt != 0 and query("c1dw_supported", h, w, c, dt) == 1
+        chunks = (query("c1dw_tile_rows", h, w, c) if tile else
+                  (1 if c1dw else query("dw_fwd_slab_rows", B, h, w, c, dt)))
+        # level 0: t4 is dropped when the backward rebuilds it (sg_rc) or there is no backward, and g2 too (the fused FFN
+        # half) wherever the backward rebuilds that as well (nbp_dgrad_sg_rc_wg)
+        drop_t4 = dt != 0 and c == 32 and (not save or self.sg_rc)
+        ffn = drop_t4 and self.fuse_ffn and (not save or self.sg_rc_wg)
+        rows_ffn = (self.fuse_ffn_rows and W.frag is not None and not drop_t4
+                    and query("ffn_rows_supported", M, c, hw, dt) == 1)
+        return BlockPlan(
+            tile=tile, c1dw=c1dw, chunks=chunks, ln_epilogue=ln_epilogue, ln_fwd=ln_fwd, drop_t4=drop_t4, ffn=ffn,
+            rows_ffn=rows_ffn, local=self._local_window(pre, h, w),
+            carry_next=(ln_fwd or rows_ffn) and next_pre is not None,
+            sg_rc_wg=drop_t4 and self.sg_rc_wg, ln_wg=dt != 0 and c == 32 and self.ln_wg,
+            # nbp_sca_dw_bwd on the stored tape, nbp_sca_c1dw_bwd_tile on the tile path
+            sca_fold=(self.sca_fold and dt != 0 and c <= 1024 and B <= 256
+                      and (not C1DW_BWD_VARIANT if tile else c % 16 == 0)),
+            grouped=dt != 0 and c % 128 == 0 and self.group_wgrad,
+            # tiled-GEMM levels (C > 64, per-64-row-tile partials); levels 0 / 1 (skinny GEMM) keep img_chan_dot
+            chandot=dt != 0 and c > 64 and hw % 64 == 0, rows_pre=self.ffn_rows_pre)
+
+    def _block_fwd(self, P, pre, x, B, h, w, c, run: _Run, next_pre=None):
+        """One NAFBlock forward (NAFNet_arch.py:60-80) along its BlockPlan.  With plan.ln_fwd the LayerNorms run in the
+        epilogue of the GEMM producing their input (nbp_gemm_res_ln): norm2 in conv3's, the next block's norm1 (next_pre)
+        in conv5's; that block then takes (n1, st1) from run.ln_carry."""
         M = B * h * w
+        hw = h * w
         dev = x.device
         E = lambda *s: torch.empty(*s, device=dev, dtype=self.adt)  # noqa: E731
         F = lambda *s: torch.empty(*s, device=dev)  # noqa: E731  (fp32 statistics)
         dt = self.dt
-        fuse_ln = self.fuse_ln_fwd and dt != 0 and len(self._W) >= 3 and c in (32, 64, 128, 256)
-        carry, self._ln_carry = self._ln_carry, None
+        W = run.w
+        plan = self._plan_block(W, B, h, w, c, pre, next_pre, run.tape is not None)
+        carry, run.ln_carry = run.ln_carry, None
         have_n1 = carry is not None and carry[0] is x
         n1, st1 = (carry[1], carry[2]) if have_n1 else (E(M, c), F(M, 2))
-        tile = len(self._W) >= 3 and self.tile_level(B, h, w, c)
-        c1dw = (not tile and self.fuse_c1dw and dt != 0 and len(self._W) >= 3
-                and query("c1dw_supported", h, w, c, dt) == 1)
-        chunks = (query("c1dw_tile_rows", h, w, c) if tile else
-                  (1 if c1dw else query("dw_fwd_slab_rows", B, h, w, c, dt)))
-        # the tile path keeps no t1 / t2 (the backward rebuilds them from n1); t2 is dropped anyway without a tape
-        t1 = None if tile else E(M, 2 * c)
-        t2 = None if tile else E(M, 2 * c)
-        g, pool = E(M, c), F(B * chunks * c)
+        # the tile path keeps no t1 / t2 (the backward rebuilds them from n1)
+        t1 = None if plan.tile else E(M, 2 * c)
+        t2 = None if plan.tile else E(M, 2 * c)
+        g, pool = E(M, c), F(B * plan.chunks * c)
         mean, a = F(B, c), F(B, c)
         y, n2, st2 = E(M, c), E(M, c), F(M, 2)
-        # t4 channel pairs interleaved (conv4 rows stored so); at C = 32 it is dropped when the backward rebuilds
-        # it (sg_rc) or there is no backward
-        drop_t4 = dt != 0 and c == 32 and (tape is None or (self.sg_rc and self.fold_ls and len(self._W) >= 3))
-        # the fused FFN half (g2 never stored) wherever the backward rebuilds g2 too (nbp_dgrad_sg_rc_wg)
-        ffn = drop_t4 and self.fuse_ffn and len(self._W) >= 3 and (tape is None or self.sg_rc_wg)
-        t4, g2 = (None if drop_t4 else E(M, 2 * c)), (None if ffn else E(M, c))
+        # t4 channel pairs interleaved (conv4 rows stored so)
+        t4, g2 = (None if plan.drop_t4 else E(M, 2 * c)), (None if plan.ffn else E(M, c))
         out = E(M, c)
-        hw = h * w
-        # deep levels (C 128 / 256 / 512): conv3 -> norm2 -> conv4 -> SimpleGate -> conv5 (-> the next norm1) as ONE
-        # row-stationary launch (nbp_ffn_rows_fwd, bitwise the launches it replaces)
-        rows_ffn = (self.fuse_ffn_rows and dt != 0 and len(self._W) >= 4 and self._W[3] is not None and t4 is not None
-                    and g2 is not None and query("ffn_rows_supported", M, c, hw, dt) == 1)
-        carry_next = (fuse_ln or rows_ffn) and next_pre is not None
-        nn1, nst1 = (E(M, c), F(M, 2)) if carry_next else (None, None)
+        nn1, nst1 = (E(M, c), F(M, 2)) if plan.carry_next else (None, None)
+        lnw, lnb = ((self._slice(P, next_pre + "norm1.weight"), self._slice(P, next_pre + "norm1.bias"))
+                    if plan.carry_next else (None, None))
         if not have_n1:
             call("ln_fwd_nhwc", x, self._slice(P, pre + "norm1.weight"), self._slice(P, pre + "norm1.bias"),
                  n1, st1, M, c, LN_EPS, dt)
-        if tile:
-            call("c1dw_fwd_tile", n1, self._slice(self._W[1], pre + "conv1.weight"), self._slice(P, pre + "conv1.bias"),
+        if plan.tile:
+            call("c1dw_fwd_tile", n1, self._slice(W.h, pre + "conv1.weight"), self._slice(P, pre + "conv1.bias"),
                  self._slice(P, pre + "conv2.weight"), self._slice(P, pre + "conv2.bias"), None, None, g, pool, B, h, w,
                  c, dt)
-        elif c1dw:
-            call("c1_dw_sg_pool", n1, self._slice(self._W[1], pre + "conv1.weight"), self._slice(P, pre + "conv1.bias"),
+        elif plan.c1dw:
+            call("c1_dw_sg_pool", n1, self._slice(W.h, pre + "conv1.weight"), self._slice(P, pre + "conv1.bias"),
                  self._slice(P, pre + "conv2.weight"), self._slice(P, pre + "conv2.bias"), t1, t2, g, pool, B, h, w,
                  c, dt)
         else:
-            self._mm(self._W, n1, c, AM_PLAIN, None, 1, pre + "conv1.weight", t1, 2 * c, CM_PLAIN, M, 2 * c,
+            self._mm(W, n1, c, AM_PLAIN, None, 1, pre + "conv1.weight", t1, 2 * c, CM_PLAIN, M, 2 * c,
                      c, bias=self._slice(P, pre + "conv1.bias"))
             call("dw_sg_pool_fwd", t1, self._slice(P, pre + "conv2.weight"), self._slice(P, pre + "conv2.bias"),
                  t2, g, pool, B, h, w, c, dt)
-        lk = self._local_window(pre, h, w)
-        if lk is None:
-            call("sca_fwd", pool, chunks, self._slice(P, pre + "sca.1.weight"), self._slice(P, pre + "sca.1.bias"),
+        if plan.local is None:
+            call("sca_fwd", pool, plan.chunks, self._slice(P, pre + "sca.1.weight"), self._slice(P, pre + "sca.1.bias"),
                  mean, a, B, hw, c)
-            gs, am, asc = g, AM_SCALE, a
+            gs, am, asc, arows = g, AM_SCALE, a, hw
         else:
             # TLSC local window (NAFNetLocal): the pool partials above are ignored; g (.) a is formed per pixel and
             # conv3 and the rest of the block run on it with a unit scale
-            gs, am, asc = self._local_sca(P, pre, g, B, h, w, c, lk, tape), AM_PLAIN, None
-            if rows_ffn:
+            gs, am, asc, arows = self._local_sca(P, pre, g, B, h, w, c, plan.local, run.tape), AM_PLAIN, None, 1
+            if plan.rows_ffn:
                 asc = torch.ones(B, c, device=dev)
-        arows = hw if lk is None else 1
-        if rows_ffn:
-            lnw, lnb = ((self._slice(P, next_pre + "norm1.weight"), self._slice(P, next_pre + "norm1.bias"))
-                        if carry_next else (None, None))
-            call("ffn_rows_fwd", gs, asc, hw, x, self._slice(self._W[3], pre + "conv3.weight"),
+        if plan.rows_ffn:
+            # conv3 -> norm2 -> conv4 -> SimpleGate -> conv5 (-> the next norm1) as ONE row-stationary launch
+            call("ffn_rows_fwd", gs, asc, hw, x, self._slice(W.frag, pre + "conv3.weight"),
                  self._slice(P, pre + "conv3.bias"), self._slice(P, pre + "beta"), self._slice(P, pre + "norm2.weight"),
-                 self._slice(P, pre + "norm2.bias"), self._slice(self._W[3], pre + "conv4.weight"),
-                 self._slice(P, pre + "conv4.bias"), self._slice(self._W[3], pre + "conv5.weight"),
+                 self._slice(P, pre + "norm2.bias"), self._slice(W.frag, pre + "conv4.weight"),
+                 self._slice(P, pre + "conv4.bias"), self._slice(W.frag, pre + "conv5.weight"),
                  self._slice(P, pre + "conv5.bias"), self._slice(P, pre + "gamma"), lnw, lnb, y, n2, st2, t4, g2, out,
                  nn1, nst1, M, c, LN_EPS, dt)
-        elif fuse_ln:
-            call("gemm_res_ln", gs, c, am, asc, arows, self._slice(self._W[1], pre + "conv3.weight"), c, y,
+        elif plan.ln_fwd:
+            call("gemm_res_ln", gs, c, am, asc, arows, self._slice(W.h, pre + "conv3.weight"), c, y,
                  M, c, c, self._slice(P, pre + "conv3.bias"), x, self._slice(P, pre + "beta"),
                  self._slice(P, pre + "norm2.weight"), self._slice(P, pre + "norm2.bias"), n2, st2, LN_EPS,
                  dt)
         else:
-            self._mm(self._W, gs, c, am, asc, arows, pre + "conv3.weight", y, c, CM_PLAIN, M, c, c,
+            self._mm(W, gs, c, am, asc, arows, pre + "conv3.weight", y, c, CM_PLAIN, M, c, c,
                      bias=self._slice(P, pre + "conv3.bias"), R=x, rscale=self._slice(P, pre + "beta"))
             call("ln_fwd_nhwc", y, self._slice(P, pre + "norm2.weight"), self._slice(P, pre + "norm2.bias"),
                  n2, st2, M, c, LN_EPS, dt)
-        if rows_ffn:
+        if plan.rows_ffn:
             pass
-        elif ffn:
-            lnw, lnb = ((self._slice(P, next_pre + "norm1.weight"), self._slice(P, next_pre + "norm1.bias"))
-                        if carry_next else (None, None))
-            call("gemm_ffn", n2, self._slice(self._W[1], pre + "conv4.weight"), self._slice(P, pre + "conv4.bias"),
-                 self._slice(self._W[1], pre + "conv5.weight"), self._slice(P, pre + "conv5.bias"), y,
+        elif plan.ffn:
+            call("gemm_ffn", n2, self._slice(W.h, pre + "conv4.weight"), self._slice(P, pre + "conv4.bias"),
+                 self._slice(W.h, pre + "conv5.weight"), self._slice(P, pre + "conv5.bias"), y,
                  self._slice(P, pre + "gamma"), lnw, lnb, out, nn1, nst1, M, c, LN_EPS, dt)
         elif dt != 0:  # SimpleGate in the GEMM epilogue
-            self._mm(self._W, n2, c, AM_PLAIN, None, 1, pre + "conv4.weight", t4, 2 * c, CM_SG, M, 2 * c, c,
+            self._mm(W, n2, c, AM_PLAIN, None, 1, pre + "conv4.weight", t4, 2 * c, CM_SG, M, 2 * c, c,
                      bias=self._slice(P, pre + "conv4.bias"), pre=g2)
         else:
-            self._mm(self._W, n2, c, AM_PLAIN, None, 1, pre + "conv4.weight", t4, 2 * c, CM_PLAIN, M, 2 * c,
+            self._mm(W, n2, c, AM_PLAIN, None, 1, pre + "conv4.weight", t4, 2 * c, CM_PLAIN, M, 2 * c,
                      c, bias=self._slice(P, pre + "conv4.bias"))
             call("sg_fwd", t4, g2, M, c, 1, dt)
-        if ffn or rows_ffn:
+        if plan.ffn or plan.rows_ffn:
             pass
-        elif carry_next:
-            call("gemm_res_ln", g2, c, AM_PLAIN, None, 1, self._slice(self._W[1], pre + "conv5.weight"), c,
-                 out, M, c, c, self._slice(P, pre + "conv5.bias"), y, self._slice(P, pre + "gamma"),
-                 self._slice(P, next_pre + "norm1.weight"), self._slice(P, next_pre + "norm1.bias"), nn1,
+        elif plan.carry_next:
+            call("gemm_res_ln", g2, c, AM_PLAIN, None, 1, self._slice(W.h, pre + "conv5.weight"), c,
+                 out, M, c, c, self._slice(P, pre + "conv5.bias"), y, self._slice(P, pre + "gamma"), lnw, lnb, nn1,
                  nst1, LN_EPS, dt)
         else:
-            self._mm(self._W, g2, c, AM_PLAIN, None, 1, pre + "conv5.weight", out, c, CM_PLAIN, M, c, c,
+            self._mm(W, g2, c, AM_PLAIN, None, 1, pre + "conv5.weight", out, c, CM_PLAIN, M, c, c,
                      bias=self._slice(P, pre + "conv5.bias"), R=y, rscale=self._slice(P, pre + "gamma"))
 
-        if carry_next:
-            self._ln_carry = (out.view(B, h, w, c), nn1, nst1)
-        if tape is not None:
-            tape.append(("block", pre, (B, h, w, c), dict(x=x, n1=n1, st1=st1, t1=t1, t2=t2, g=g, mean=mean, a=a, y=y,
-                                                           n2=n2, st2=st2, t4=t4, g2=g2)))
-        return self._ln_carry[0] if self._ln_carry is not None else out.view(B, h, w, c)
+        out = out.view(B, h, w, c)
+        if plan.carry_next:
+            run.ln_carry = (out, nn1, nst1)
+        if run.tape is not None:
+            run.tape.append(("block", pre, (B, h, w, c), dict(x=x, n1=n1, st1=st1, t1=t1, t2=t2, g=g, mean=mean, a=a,
+                                                              y=y, n2=n2, st2=st2, t4=t4, g2=g2), plan))
+        return out
 
     def tile_level(self, B: int, h: int, w: int, c: int) -> bool:
         """Whether a block of this level takes the tile path (nbp_c1dw_fwd_tile / nbp_c1dw_bwd_tile: t1 / t2 rebuilt on
@@ -663,23 +715,23 @@ class NAFNet(nn.Module):
              B, h, w, c, k1, k2, dt)
         return ga
 
-    def _down_fwd(self, P, i, x, B, h, w, c, tape):
+    def _down_fwd(self, P, i, x, B, h, w, c, run: _Run):
         ho, wo = h // 2, w // 2
         M = B * ho * wo
         out = torch.empty(B, ho, wo, 2 * c, device=x.device, dtype=self.adt)
-        self._mm(self._W, x, 0, AM_S2D, None, 1, f"downs.{i}.weight", out, 2 * c, CM_PLAIN, M, 2 * c, 4 * c, ho, wo,
+        self._mm(run.w, x, 0, AM_S2D, None, 1, f"downs.{i}.weight", out, 2 * c, CM_PLAIN, M, 2 * c, 4 * c, ho, wo,
                  c, bias=self._slice(P, f"downs.{i}.bias"))
-        if tape is not None:
-            tape.append(("down", i, (B, h, w, c), x))
+        if run.tape is not None:
+            run.tape.append(("down", i, (B, h, w, c), x))
         return out
 
-    def _up_fwd(self, P, i, x, skip, B, h, w, chan, tape):
+    def _up_fwd(self, P, i, x, skip, B, h, w, chan, run: _Run):
         M = B * h * w
         out = torch.empty(B, 2 * h, 2 * w, chan // 2, device=x.device, dtype=self.adt)
-        self._mm(self._W, x, chan, AM_PLAIN, None, 1, f"ups.{i}.0.weight", out, 0, CM_D2S, M, 2 * chan, chan, h, w,
+        self._mm(run.w, x, chan, AM_PLAIN, None, 1, f"ups.{i}.0.weight", out, 0, CM_D2S, M, 2 * chan, chan, h, w,
                  chan // 2, R=skip)
-        if tape is not None:
-            tape.append(("up", i, (B, h, w, chan), x))
+        if run.tape is not None:
+            run.tape.append(("up", i, (B, h, w, chan), x))
         return out
 
     # ------------------------------------------------------------------ backward
@@ -688,36 +740,29 @@ class NAFNet(nn.Module):
         """Walk the tape in reverse.  Writes every parameter gradient (exactly once) into dflat, calls
         hook(stage) as each stage's gradient slice is complete, returns d(input) or None.  Runs in the precision the
         tape's forward ran in (Tape.precision): the backward of an AMP step is called outside the autocast region
-        (image_restoration_model.py:306-310), and autograd's backward thread does not see the forward's region either."""
+        (image_restoration_model.py:306-310), and autograd's backward thread does not see the forward's region either.
+        Every block takes the path its tape record planned (BlockPlan), whatever the switches say by now."""
         P = self.flat.data if flat is None else flat
         prec = getattr(tape, "precision", None)
         with self._pinned(self.resolved_precision() if prec is None else prec):
-            self._keep = []
+            run = _Run(next((rec[1] for rec in tape if rec[0] == "weights"), Weights(P)))
             call("grad_reduce_defer")
             try:
-                return self._walk_backward(tape, dout, dflat, need_dx, P, hook)
+                return self._walk_backward(tape, dout, dflat, need_dx, P, hook, run)
             finally:
-                if self._grouping:  # an error inside a grouped level: launch what is queued so the library state is reset
-                    self._grouping = False
+                if run.grouping:  # an error inside a grouped level: launch what is queued so the library state is reset
                     call("wgrad_group", 0)
                 call("grad_reduce_flush", 1)
-                self._keep = None
 
-    def _level_grouped(self, c: int) -> bool:
-        return self.dt != 0 and c % 128 == 0 and self.group_wgrad
-
-    def _close_level(self, pending: List[str], hook):
+    def _close_level(self, run: _Run, pending: List[str], hook):
         """Launch the level's queued weight gradients, then complete its stages (flush + DP hooks) in order."""
-        self._grouping = False
+        run.grouping = False
         call("wgrad_group", 0)
         for name in pending:
-            self._stage_done(name, hook)
+            self._stage_done(run, name, hook)
 
-    def _walk_backward(self, tape, dout, dflat, need_dx, P, hook):
-        Wt = (P,)
-        for rec in tape:
-            if rec[0] == "weights":
-                Wt = rec[1]
+    def _walk_backward(self, tape, dout, dflat, need_dx, P, hook, run: _Run):
+        Wt = run.w
         dfeat = None
         dskips: List[torch.Tensor] = []
         dx_img = None
@@ -728,35 +773,35 @@ class NAFNet(nn.Module):
         for idx, rec in enumerate(recs):
             kind = rec[0]
             if pend is not None and kind != "block":  # not expected (deferral looks ahead to a block): resolve it
-                dfeat, pend = self._conv1_bwd(P, Wt, dflat, **pend), None
-            grouped = kind == "block" and self._level_grouped(rec[2][3])
+                dfeat, pend = self._conv1_bwd(P, run, dflat, **pend), None
+            grouped = kind == "block" and rec[4].grouped
             if level is not None and not (grouped and rec[2][3] == level_c):
-                self._close_level(level, hook)
+                self._close_level(run, level, hook)
                 level = None
             if grouped and level is None:
                 call("wgrad_group", 1)
-                self._grouping = True
+                run.grouping = True
                 level, level_c = [], rec[2][3]
             if kind == "ending":
                 feat, (B, Ci, H0, W0, Hp, Wp, w) = rec[1], rec[2]
                 dfeat = torch.empty(B, Hp, Wp, w, device=dout.device, dtype=self.adt)
-                ws = self._ws(query("ending_bwd_workspace_floats", B, Ci, H0, W0, w), dout.device)
+                ws = self._ws(run, query("ending_bwd_workspace_floats", B, Ci, H0, W0, w), dout.device)
                 call("ending_bwd", dout, feat, self._slice(P, "ending.weight"), dfeat,
                      self._slice(dflat, "ending.weight"), self._slice(dflat, "ending.bias"), ws, B, Ci, H0, W0, Hp,
                      Wp, w, self.dt)
-                self._stage_done("ending", hook)
+                self._stage_done(run, "ending", hook)
             elif kind == "block":
-                pre, geo, S = rec[1], rec[2], rec[3]
+                pre, geo, S, plan = rec[1], rec[2], rec[3], rec[4]
                 # defer into the preceding block of the same (grouped) level when that one takes the row-stationary
                 # backward: the norm1 gradients of this block then land before the level closes
                 nxt = recs[idx + 1] if idx + 1 < len(recs) else None
-                defer = (self.ffn_rows_pre and level is not None and nxt is not None and nxt[0] == "block"
-                         and tuple(nxt[2]) == tuple(geo) and self._rows_ok(Wt, nxt[3], geo))
-                dfeat, pend = self._block_bwd(P, Wt, dflat, pre, geo, S, dfeat, pend, defer)
+                defer = (plan.rows_pre and level is not None and nxt is not None and nxt[0] == "block"
+                         and tuple(nxt[2]) == tuple(geo) and nxt[4].rows_ffn)
+                dfeat, pend = self._block_bwd(P, Wt, dflat, pre, geo, S, plan, run, dfeat, pend, defer)
                 if level is not None:
                     level.append(pre[:-1])
                 else:
-                    self._stage_done(pre[:-1], hook)
+                    self._stage_done(run, pre[:-1], hook)
             elif kind == "up":
                 i, (B, h, w, chan), x = rec[1], rec[2], rec[3]
                 dskips.append(dfeat)  # d(skip) = d(up output): the skip add is an identity branch
@@ -764,9 +809,9 @@ class NAFNet(nn.Module):
                 dx = torch.empty(B, h, w, chan, device=dout.device, dtype=self.adt)
                 self._mm(Wt, dfeat, 0, AM_S2D, None, 1, f"ups.{i}.0.weight", dx, chan, CM_PLAIN, M, chan, 2 * chan,
                          h, w, chan // 2, dgrad=True)
-                self._wgrad(dfeat, 0, AM_S2D, x, chan, AM_PLAIN, None, 1, M, 2 * chan, chan, h, w, chan // 2, 0,
+                self._wgrad(run, dfeat, 0, AM_S2D, x, chan, AM_PLAIN, None, 1, M, 2 * chan, chan, h, w, chan // 2, 0,
                             self._slice(dflat, f"ups.{i}.0.weight"), None)
-                self._stage_done(f"ups.{i}", hook)
+                self._stage_done(run, f"ups.{i}", hook)
                 dfeat = dx
             elif kind == "down":
                 i, (B, h, w, c), x = rec[1], rec[2], rec[3]
@@ -777,108 +822,104 @@ class NAFNet(nn.Module):
                 # d enc = D2S(dout . Wd) + d skip
                 self._mm(Wt, dfeat, 2 * c, AM_PLAIN, None, 1, f"downs.{i}.weight", dx, 0, CM_D2S, M, 4 * c, 2 * c,
                          ho, wo, c, R=dskip, dgrad=True)
-                self._wgrad(dfeat, 2 * c, AM_PLAIN, x, 0, AM_S2D, None, 1, M, 2 * c, 4 * c, ho, wo, 0, c,
+                self._wgrad(run, dfeat, 2 * c, AM_PLAIN, x, 0, AM_S2D, None, 1, M, 2 * c, 4 * c, ho, wo, 0, c,
                             self._slice(dflat, f"downs.{i}.weight"), self._slice(dflat, f"downs.{i}.bias"))
-                self._stage_done(f"downs.{i}", hook)
+                self._stage_done(run, f"downs.{i}", hook)
                 dfeat = dx
             elif kind == "intro":
                 x, (B, Ci, H0, W0, Hp, Wp, w) = rec[1], rec[2]
-                ws = self._ws(query("intro_bwd_workspace_floats", B, Ci, Hp, Wp, w), dout.device)
+                ws = self._ws(run, query("intro_bwd_workspace_floats", B, Ci, Hp, Wp, w), dout.device)
                 if need_dx:
                     dx_img = torch.empty(B, Ci, H0, W0, device=dout.device)
                 call("intro_bwd", x, dfeat, self._slice(P, "intro.weight"), self._slice(dflat, "intro.weight"),
                      self._slice(dflat, "intro.bias"), dx_img, ws, B, Ci, H0, W0, Hp, Wp, w, self.dt)
-                self._stage_done("intro", hook)
+                self._stage_done(run, "intro", hook)
         if level is not None:
-            self._close_level(level, hook)
+            self._close_level(run, level, hook)
         if need_dx:
             # global residual x + inp (NAFNet_arch.py:153): d inp += d out
             call("add", dx_img, dout, dx_img, dx_img.numel(), 0)
         return dx_img
 
-    def _stage_done(self, name, hook):
-        # the stage's queued gradient reductions run before anyone (the DP all-reduce hook) reads its slice; without a
-        # hook they all wait for the backward's final flush (_LATE_FLUSH)
-        if hook is None and _LATE_FLUSH:
+    def _stage_done(self, run: _Run, name, hook):
+        """With a gradient-ready hook (the bucketed DP all-reduce) the stage's queued gradient reductions run before the
+        hook reads its slice.  Without one nobody reads a slice early, and every deferred reduction waits for the
+        backward's final flush: 26 latency-bound reduce launches per step become a few full ones."""
+        if hook is None:
             return
         call("grad_reduce_flush", 0)
-        self._keep.clear()
-        if hook is not None:
-            hook(self.stages[name])
+        run.keep.clear()
+        hook(self.stages[name])
 
-    def _ws(self, n, dev):
+    def _ws(self, run: _Run, n, dev):
         """fp32 workspace that stays referenced until the next gradient-reduction flush (deferred reductions read
         it after this call returns)."""
         t = torch.empty(n, device=dev)
-        if self._keep is not None:
-            self._keep.append(t)
+        run.keep.append(t)
         return t
 
-    def _wgrad(self, G, ldg, gmode, X, ldx, xmode, xscale, rows, M, N, K, gh, gw, csg, csx, dW, db, dtype=None):
+    def _wgrad(self, run: _Run, G, ldg, gmode, X, ldx, xmode, xscale, rows, M, N, K, gh, gw, csg, csx, dW, db):
         """Weight gradient (its output only feeds the stage's deferred reductions)."""
         n_ws = query("wgrad_workspace_floats", M, N, K)
-        ws = self._ws(n_ws, G.device)
-        if self._grouping and self._keep is not None:  # the launch is deferred to the level's end: keep the operands
-            self._keep.extend(t for t in (G, X, xscale) if t is not None)
+        ws = self._ws(run, n_ws, G.device)
+        if run.grouping:  # the launch is deferred to the level's end: keep the operands
+            run.keep.extend(t for t in (G, X, xscale) if t is not None)
         call("wgrad_f32", G, ldg, gmode, X, ldx, xmode, xscale, rows, M, N, K, gh, gw, csg, csx, dW, db, ws,
-             n_ws, self.dt if dtype is None else dtype)
+             n_ws, self.dt)
 
     def _reduce(self, slab, S, L, out):
         call("reduce_slab", slab, S, L, out)
 
-    def _ffn_bwd_launches(self, P, Wt, dflat, pre, B, h, w, c, S, dout):
+    def _wgrad_layer_scale(self, run: _Run, P, dflat, pre, conv, scale, G, X, xmode, xscale, rows, M, c, UV=None):
+        """The gradients of a layer-scaled conv, out = r + scale (.) conv(X): U = G^T X and V = colsum G (made here
+        unless UV holds them), then dW = scale (.) U, db = scale (.) V, dscale = rowsum(W (.) U) + b (.) V
+        (nbp_layer_scale_grad, after the reductions).  At C >= 128 the U launch is queued into the level's grouped one."""
+        if UV is None:
+            UV = self._ws(run, c * c, G.device), self._ws(run, c, G.device)
+            self._wgrad(run, G, c, AM_PLAIN, X, c, xmode, xscale, rows, M, c, c, 0, 0, 0, 0, *UV)
+        call("layer_scale_grad", *UV, self._slice(P, pre + conv + ".weight"), self._slice(P, pre + conv + ".bias"),
+             self._slice(P, pre + scale), self._slice(dflat, pre + conv + ".weight"),
+             self._slice(dflat, pre + conv + ".bias"), self._slice(dflat, pre + scale), c, c)
+
+    def _ffn_bwd_launches(self, P, run: _Run, dflat, pre, B, h, w, c, S, plan: BlockPlan, dout):
         """The FFN half's backward as separate launches; returns (dy, dh, SCA channel-dot slab, its chunks per image)."""
         M = B * h * w
         HW = h * w
         dev = dout.device
         E = lambda *s: torch.empty(*s, device=dev, dtype=self.adt)  # noqa: E731
-        F = lambda *s: self._ws(math.prod(s), dev)  # noqa: E731  (slabs live until the stage's flush)
+        F = lambda *s: self._ws(run, math.prod(s), dev)  # noqa: E731  (slabs live until the stage's flush)
         dt = self.dt
-        # out = y + gamma * conv5(g2): no stored pre-activation, no scaled-gradient pass.  dg2 = (gamma (.) dout) W5
-        # (gamma as the A-operand column scale); U5 = dout^T g2, V5 = colsum dout feed dW5 = gamma (.) U5,
-        # db5 = gamma (.) V5, dgamma = rowsum(W5 (.) U5) + b5 (.) V5 (nbp_layer_scale_grad, after the reductions).
+        Wt = run.w
+        # out = y + gamma * conv5(g2): no stored pre-activation, no scaled-gradient pass.  dg2 = (gamma (.) dout) W5:
+        # gamma / beta are already in the transposed 16-bit weights; fp32 takes gamma as the A-operand column scale
         dt4 = E(M, 2 * c)
-        folded = len(Wt) >= 3 and self.fold_ls  # gamma / beta already in the transposed bf16 weights
-        U5, V5 = F(c * c), F(c)
-        wg_folded = False
-        if dt != 0:  # SimpleGate backward in the dgrad epilogue: dg2 never materialises
-            if S["t4"] is None:  # t4 = conv4(n2) rebuilt per tile inside the dgrad (level 0, folded layer scale)
-                assert folded and c == 32
-                args = (dout, c, self._slice(Wt[2], pre + "conv5.weight"), c, S["n2"],
-                        self._slice(Wt[1], pre + "conv4.weight"), self._slice(P, pre + "conv4.bias"), dt4, M, c, c)
-                if self.sg_rc_wg:  # + U5 / V5 and conv4's dW / db from the same tiles
-                    n_ws = query("dgrad_sg_rc_wg_workspace_floats", M, c)
-                    call("dgrad_sg_rc_wg", *args, U5, V5, self._slice(dflat, pre + "conv4.weight"),
-                         self._slice(dflat, pre + "conv4.bias"), F(n_ws), n_ws, dt)
-                    wg_folded = True
-                else:
-                    call("dgrad_sg_rc", *args, dt)
-            elif folded:
-                self._mm(Wt, dout, c, AM_PLAIN, None, 1, pre + "conv5.weight", dt4, 2 * c, CM_SGBWD, M, c, c,
-                         R=S["t4"], dgrad=True)
+        UV5 = None
+        if plan.drop_t4:  # t4 = conv4(n2) rebuilt per tile inside the dgrad (level 0)
+            args = (dout, c, self._slice(Wt.ht, pre + "conv5.weight"), c, S["n2"],
+                    self._slice(Wt.h, pre + "conv4.weight"), self._slice(P, pre + "conv4.bias"), dt4, M, c, c)
+            if plan.sg_rc_wg:  # + U5 / V5 and conv4's dW / db from the same tiles
+                UV5 = F(c * c), F(c)
+                n_ws = query("dgrad_sg_rc_wg_workspace_floats", M, c)
+                call("dgrad_sg_rc_wg", *args, *UV5, self._slice(dflat, pre + "conv4.weight"),
+                     self._slice(dflat, pre + "conv4.bias"), F(n_ws), n_ws, dt)
             else:
-                self._mm(Wt, dout, c, AM_SCALE, self._slice(P, pre + "gamma"), M, pre + "conv5.weight", dt4, 2 * c,
-                         CM_SGBWD, M, c, c, R=S["t4"], dgrad=True)
+                call("dgrad_sg_rc", *args, dt)
+        elif dt != 0:  # SimpleGate backward in the dgrad epilogue: dg2 never materialises
+            self._mm(Wt, dout, c, AM_PLAIN, None, 1, pre + "conv5.weight", dt4, 2 * c, CM_SGBWD, M, c, c,
+                     R=S["t4"], dgrad=True)
         else:
             dg2 = E(M, c)
             self._mm(Wt, dout, c, AM_SCALE, self._slice(P, pre + "gamma"), M, pre + "conv5.weight", dg2, c, CM_PLAIN,
                      M, c, c, dgrad=True)
             call("sg_bwd", dg2, S["t4"], dt4, M, c, 1, dt)
-        # at C >= 128 the wide weight gradients below are queued into the level's grouped launch (_walk_backward)
-        if not wg_folded:
-            self._wgrad(dout, c, AM_PLAIN, S["g2"], c, AM_PLAIN, None, 1, M, c, c, 0, 0, 0, 0, U5, V5)
-        call("layer_scale_grad", U5, V5, self._slice(P, pre + "conv5.weight"), self._slice(P, pre + "conv5.bias"),
-             self._slice(P, pre + "gamma"), self._slice(dflat, pre + "conv5.weight"),
-             self._slice(dflat, pre + "conv5.bias"), self._slice(dflat, pre + "gamma"), c, c)
+        self._wgrad_layer_scale(run, P, dflat, pre, "conv5", "gamma", dout, S["g2"], AM_PLAIN, None, 1, M, c, UV5)
         # conv4 input gradient + norm2 backward + residual
-        # LN backward in the dgrad's epilogue (dn never stored): skinny kernel at C 32 / 64, 64 x 128 tiles at 128
-        fuse_ln = dt != 0 and c in (32, 64, 128, 256)
         dy = E(M, c)
-        if not wg_folded:
-            self._wgrad(dt4, 2 * c, AM_PLAIN, S["n2"], c, AM_PLAIN, None, 1, M, 2 * c, c, 0, 0, 0, 0,
+        if not plan.sg_rc_wg:
+            self._wgrad(run, dt4, 2 * c, AM_PLAIN, S["n2"], c, AM_PLAIN, None, 1, M, 2 * c, c, 0, 0, 0, 0,
                         self._slice(dflat, pre + "conv4.weight"), self._slice(dflat, pre + "conv4.bias"))
-        if fuse_ln:
-            self._dgrad_ln(Wt, dflat, P, pre, "conv4.weight", "norm2", dt4, S["y"].reshape(M, c), S["st2"], dout, dy,
+        if plan.ln_epilogue:  # LN backward in the dgrad's epilogue (dn never stored)
+            self._dgrad_ln(run, dflat, P, pre, "conv4.weight", "norm2", dt4, S["y"].reshape(M, c), S["st2"], dout, dy,
                            M, c)
         else:
             dn2 = E(M, c)
@@ -892,39 +933,25 @@ class NAFNet(nn.Module):
             self._reduce(sb, lg, c, self._slice(dflat, pre + "norm2.bias"))
         # y = x + beta * conv3(h), h = g (.) a: same layer-scale identity as conv5 (dh = (beta (.) dy) W3)
         dh = E(M, c)
-        # tiled-GEMM levels (C > 64): the SCA channel dot sum_p dh (.) g rides in the dgrad epilogue (CM_CHANDOT,
-        # per-64-row-tile partials); levels 0/1 (skinny GEMM) keep img_chan_dot
-        chandot = folded and c > 64 and HW % 64 == 0
-        if chandot:
+        if plan.chandot:  # the SCA channel dot sum_p dh (.) g rides in the dgrad epilogue
             chunks = HW // 64
             da_slab = F(B * chunks * c)
-            call("gemm_bf16", dy, c, AM_PLAIN, None, HW, dt, self._slice(Wt[2], pre + "conv3.weight"), c, dh, c,
+            call("gemm_bf16", dy, c, AM_PLAIN, None, HW, dt, self._slice(Wt.ht, pre + "conv3.weight"), c, dh, c,
                  CM_CHANDOT, dt, M, c, c, 0, 0, 0, None, S["g"], None, da_slab)
-        elif folded:
+        elif dt != 0:
             self._mm(Wt, dy, c, AM_PLAIN, None, 1, pre + "conv3.weight", dh, c, CM_PLAIN, M, c, c, dgrad=True)
         else:
             self._mm(Wt, dy, c, AM_SCALE, self._slice(P, pre + "beta"), M, pre + "conv3.weight", dh, c, CM_PLAIN, M,
                      c, c, dgrad=True)
-        U3, V3 = F(c * c), F(c)
-        self._wgrad(dy, c, AM_PLAIN, S["g"], c, AM_SCALE, S["a"], HW, M, c, c, 0, 0, 0, 0, U3, V3)
-        call("layer_scale_grad", U3, V3, self._slice(P, pre + "conv3.weight"), self._slice(P, pre + "conv3.bias"),
-             self._slice(P, pre + "beta"), self._slice(dflat, pre + "conv3.weight"),
-             self._slice(dflat, pre + "conv3.bias"), self._slice(dflat, pre + "beta"), c, c)
+        self._wgrad_layer_scale(run, P, dflat, pre, "conv3", "beta", dy, S["g"], AM_SCALE, S["a"], HW, M, c)
         # SCA
-        if not chandot:
+        if not plan.chandot:
             chunks = query("dw_chunks", B, h, w, c, 0)
             da_slab = F(B * chunks * c)
             call("img_chan_dot", dh, S["g"], da_slab, B, h, w, c, dt)
         return dy, dh, da_slab, chunks
 
-    def _rows_ok(self, Wt, S, geo) -> bool:
-        """Whether a block's FFN backward takes the row-stationary launch (nbp_ffn_rows_bwd)."""
-        B, h, w, c = geo
-        return (self.fuse_ffn_rows and self.dt != 0 and len(Wt) >= 5 and Wt[4] is not None and self.fold_ls
-                and S["t4"] is not None and S["g2"] is not None
-                and query("ffn_rows_supported", B * h * w, c, h * w, self.dt) == 1)
-
-    def _ffn_bwd_rows(self, P, Wt, dflat, pre, B, h, w, c, S, dout, pend=None):
+    def _ffn_bwd_rows(self, P, run: _Run, dflat, pre, B, h, w, c, S, dout, pend=None):
         """The FFN half's backward in one row-stationary launch (nbp_ffn_rows_bwd: dt4, dy, dh bitwise the launches; the
         norm2 weight / bias and SCA channel-dot partials per 32-row block), then the weight gradients it feeds queued
         as in _ffn_bwd_launches.  With pend (the following block's deferred conv1 input gradient, dout None) the launch
@@ -934,8 +961,9 @@ class NAFNet(nn.Module):
         HW = h * w
         dev = (dout if dout is not None else pend["dt1"]).device
         E = lambda *s: torch.empty(*s, device=dev, dtype=self.adt)  # noqa: E731
-        F = lambda *s: self._ws(math.prod(s), dev)  # noqa: E731  (slabs live until the stage's flush)
+        F = lambda *s: self._ws(run, math.prod(s), dev)  # noqa: E731  (slabs live until the stage's flush)
         dt = self.dt
+        Wf = run.w.frag_t
         nb = M // 32
         dt4, dy, dh = E(M, 2 * c), E(M, c), E(M, c)
         sw, sb, da_slab = F(nb * c), F(nb * c), F(nb * c)
@@ -944,131 +972,116 @@ class NAFNet(nn.Module):
             q = pend["pre"]
             dout = E(M, c)
             sw1, sb1 = F(nb * c), F(nb * c)
-            pre_args = (pend["dt1"], self._slice(Wt[4], q + "conv1.weight"), pend["x"], pend["st1"],
+            pre_args = (pend["dt1"], self._slice(Wf, q + "conv1.weight"), pend["x"], pend["st1"],
                         self._slice(P, q + "norm1.weight"), pend["dy"], dout, sw1, sb1)
         call("ffn_rows_bwd", None if pend is not None else dout, S["t4"], S["y"].reshape(M, c), S["st2"],
-             self._slice(P, pre + "norm2.weight"), S["g"], self._slice(Wt[4], pre + "conv5.weight"),
-             self._slice(Wt[4], pre + "conv4.weight"), self._slice(Wt[4], pre + "conv3.weight"), dt4, dy, dh, sw, sb,
+             self._slice(P, pre + "norm2.weight"), S["g"], self._slice(Wf, pre + "conv5.weight"),
+             self._slice(Wf, pre + "conv4.weight"), self._slice(Wf, pre + "conv3.weight"), dt4, dy, dh, sw, sb,
              da_slab, *pre_args, M, c, HW, dt)
         if pend is not None:
-            self._reduce(sw1, nb, c, self._slice(dflat, pend["pre"] + "norm1.weight"))
-            self._reduce(sb1, nb, c, self._slice(dflat, pend["pre"] + "norm1.bias"))
-        U5, V5 = F(c * c), F(c)
-        self._wgrad(dout, c, AM_PLAIN, S["g2"], c, AM_PLAIN, None, 1, M, c, c, 0, 0, 0, 0, U5, V5)
-        call("layer_scale_grad", U5, V5, self._slice(P, pre + "conv5.weight"), self._slice(P, pre + "conv5.bias"),
-             self._slice(P, pre + "gamma"), self._slice(dflat, pre + "conv5.weight"),
-             self._slice(dflat, pre + "conv5.bias"), self._slice(dflat, pre + "gamma"), c, c)
-        self._wgrad(dt4, 2 * c, AM_PLAIN, S["n2"], c, AM_PLAIN, None, 1, M, 2 * c, c, 0, 0, 0, 0,
+            self._reduce(sw1, nb, c, self._slice(dflat, q + "norm1.weight"))
+            self._reduce(sb1, nb, c, self._slice(dflat, q + "norm1.bias"))
+        self._wgrad_layer_scale(run, P, dflat, pre, "conv5", "gamma", dout, S["g2"], AM_PLAIN, None, 1, M, c)
+        self._wgrad(run, dt4, 2 * c, AM_PLAIN, S["n2"], c, AM_PLAIN, None, 1, M, 2 * c, c, 0, 0, 0, 0,
                     self._slice(dflat, pre + "conv4.weight"), self._slice(dflat, pre + "conv4.bias"))
         self._reduce(sw, nb, c, self._slice(dflat, pre + "norm2.weight"))
         self._reduce(sb, nb, c, self._slice(dflat, pre + "norm2.bias"))
-        U3, V3 = F(c * c), F(c)
-        self._wgrad(dy, c, AM_PLAIN, S["g"], c, AM_SCALE, S["a"], HW, M, c, c, 0, 0, 0, 0, U3, V3)
-        call("layer_scale_grad", U3, V3, self._slice(P, pre + "conv3.weight"), self._slice(P, pre + "conv3.bias"),
-             self._slice(P, pre + "beta"), self._slice(dflat, pre + "conv3.weight"),
-             self._slice(dflat, pre + "conv3.bias"), self._slice(dflat, pre + "beta"), c, c)
+        self._wgrad_layer_scale(run, P, dflat, pre, "conv3", "beta", dy, S["g"], AM_SCALE, S["a"], HW, M, c)
         return dy, dh, da_slab, HW // 32, dout
 
-    def _block_bwd(self, P, Wt, dflat, pre, geo, S, dout, pend=None, defer=False):
-        """One block's backward.  dout None: the following block's conv1 input gradient is pending (pend) and made by
-        this block's row-stationary launch.  defer: this block's own conv1 input gradient + norm1 backward is left
-        pending for the preceding block.  Returns (dx or None, pending or None)."""
+    def _block_bwd(self, P, Wt, dflat, pre, geo, S, plan: BlockPlan, run: _Run, dout, pend=None, defer=False):
+        """One block's backward along the plan its forward recorded.  dout None: the following block's conv1 input
+        gradient is pending (pend) and made by this block's row-stationary launch.  defer: this block's own conv1 input
+        gradient + norm1 backward is left pending for the preceding block.  Returns (dx or None, pending or None)."""
         B, h, w, c = geo
         M = B * h * w
         HW = h * w
         dt = self.dt
         # the FFN half's backward: conv5 dgrad + SimpleGate backward, conv4 dgrad + norm2 backward, conv3 dgrad (+ the SCA
         # channel-dot partials) and the weight gradients they feed
-        rows = self._rows_ok(Wt, S, geo)
-        if pend is not None and not rows:  # not expected (the walker's look-ahead uses the same test): resolve it here
-            dout, pend = self._conv1_bwd(P, Wt, dflat, **pend), None
-        if rows:
-            dy, dh, da_slab, chunks, dout = self._ffn_bwd_rows(P, Wt, dflat, pre, B, h, w, c, S,
+        if pend is not None and not plan.rows_ffn:  # not expected (the walker's look-ahead reads the same plan): resolve
+            dout, pend = self._conv1_bwd(P, run, dflat, **pend), None
+        if plan.rows_ffn:
+            dy, dh, da_slab, chunks, dout = self._ffn_bwd_rows(P, run, dflat, pre, B, h, w, c, S,
                                                                None if pend is not None else dout.reshape(M, c), pend)
         else:
             dout = dout.reshape(M, c)
-            dy, dh, da_slab, chunks = self._ffn_bwd_launches(P, Wt, dflat, pre, B, h, w, c, S, dout)
+            dy, dh, da_slab, chunks = self._ffn_bwd_launches(P, run, dflat, pre, B, h, w, c, S, plan, dout)
         dev = dout.device
         E = lambda *s: torch.empty(*s, device=dev, dtype=self.adt)  # noqa: E731
-        F = lambda *s: self._ws(math.prod(s), dev)  # noqa: E731  (slabs live until the stage's flush)
+        F = lambda *s: self._ws(run, math.prod(s), dev)  # noqa: E731  (slabs live until the stage's flush)
         # ds = da . W_sca and the SCA weight gradients dW = da^T mean, db = colsum(da) in one launch (or inside the
         # depthwise backward below)
-        env = __import__("os").environ
-        sca_fold = self.sca_fold and dt != 0 and c <= 1024 and B <= 256 and (
-            (S["t1"] is not None and c % 16 == 0)  # nbp_sca_dw_bwd
-            or (S["t1"] is None and not env.get("NBP_C1DW_BWD_TH") and not env.get("NBP_C1DW_BWD_BAL")))  # the tile
-        if not sca_fold:
+        sca_args = (da_slab, chunks, self._slice(P, pre + "sca.1.weight"), S["mean"])
+        dsca = (self._slice(dflat, pre + "sca.1.weight"), self._slice(dflat, pre + "sca.1.bias"))
+        if not plan.sca_fold:
             ds = F(B, c)
-            call("sca_bwd_fused", da_slab, chunks, self._slice(P, pre + "sca.1.weight"), S["mean"], ds,
-                 self._slice(dflat, pre + "sca.1.weight"), self._slice(dflat, pre + "sca.1.bias"), B, c)
+            call("sca_bwd_fused", *sca_args, ds, *dsca, B, c)
         # SimpleGate + depthwise conv2 (fused when the channel slicing allows: dt2 stays in LDS)
         dt1 = E(M, 2 * c)
-        if S["t1"] is None:  # levels 0 / 1 tile path: t1 / t2 rebuilt from n1 on chip (nbp_c1dw_bwd_tile)
+        if plan.tile:  # t1 / t2 rebuilt from n1 on chip (nbp_c1dw_bwd_tile)
             ws = F(query("c1dw_bwd_workspace_floats", B, h, w, c))
-            tail = (S["n1"], self._slice(Wt[1], pre + "conv1.weight"), self._slice(P, pre + "conv1.bias"),
+            tail = (S["n1"], self._slice(Wt.h, pre + "conv1.weight"), self._slice(P, pre + "conv1.bias"),
                     self._slice(P, pre + "conv2.weight"), self._slice(P, pre + "conv2.bias"), dt1,
                     self._slice(dflat, pre + "conv2.weight"), self._slice(dflat, pre + "conv2.bias"), ws, B, h, w, c, dt)
-            if sca_fold:
-                call("sca_c1dw_bwd_tile", dh, S["a"], da_slab, chunks, self._slice(P, pre + "sca.1.weight"), S["mean"],
-                     self._slice(dflat, pre + "sca.1.weight"), self._slice(dflat, pre + "sca.1.bias"), *tail)
+            if plan.sca_fold:
+                call("sca_c1dw_bwd_tile", dh, S["a"], *sca_args, *dsca, *tail)
             else:
                 call("c1dw_bwd_tile", dh, S["a"], ds, *tail)
         else:
             ws = F(query("dw_bwd_workspace_floats", B, h, w, c))
             dw_args = (S["t1"], self._slice(P, pre + "conv2.weight"), dt1, self._slice(dflat, pre + "conv2.weight"),
                        self._slice(dflat, pre + "conv2.bias"), ws, B, h, w, c, dt)
-        if sca_fold and S["t1"] is not None:
-            call("sca_dw_bwd", dh, S["a"], da_slab, chunks, self._slice(P, pre + "sca.1.weight"), S["mean"],
-                 self._slice(dflat, pre + "sca.1.weight"), self._slice(dflat, pre + "sca.1.bias"), S["t2"], *dw_args)
-        elif S["t1"] is not None and c % (16 if dt != 0 else 8) == 0:
-            call("sca_sg_dw_bwd", dh, S["a"], ds, S["t2"], *dw_args)
-        elif S["t1"] is not None:
-            dt2 = E(M, 2 * c)
-            call("sca_sg_bwd", dh, S["a"], ds, S["t2"], dt2, M, c, HW, dt)
-            call("dw_bwd", dt2, *dw_args)
+            if plan.sca_fold:
+                call("sca_dw_bwd", dh, S["a"], *sca_args, *dsca, S["t2"], *dw_args)
+            elif c % (16 if dt != 0 else 8) == 0:
+                call("sca_sg_dw_bwd", dh, S["a"], ds, S["t2"], *dw_args)
+            else:
+                dt2 = E(M, 2 * c)
+                call("sca_sg_bwd", dh, S["a"], ds, S["t2"], dt2, M, c, HW, dt)
+                call("dw_bwd", dt2, *dw_args)
         # conv1 input gradient + norm1 backward + residual
-        if dt != 0 and c == 32 and self.ln_wg:  # + conv1's dW / db from the same tiles (n1 rebuilt from x / stats)
+        if plan.ln_wg:  # + conv1's dW / db from the same tiles (n1 rebuilt from x / stats)
             dx = E(M, c)
             n_ws = query("dgrad_ln_bwd_wg_workspace_floats", M, c)
-            call("dgrad_ln_bwd_wg", dt1, 2 * c, self._slice(Wt[2], pre + "conv1.weight"), 2 * c, M, c, 2 * c,
+            call("dgrad_ln_bwd_wg", dt1, 2 * c, self._slice(Wt.ht, pre + "conv1.weight"), 2 * c, M, c, 2 * c,
                  S["x"].reshape(M, c), S["st1"], self._slice(P, pre + "norm1.weight"),
                  self._slice(P, pre + "norm1.bias"), dy, dx, self._slice(dflat, pre + "norm1.weight"),
                  self._slice(dflat, pre + "norm1.bias"), self._slice(dflat, pre + "conv1.weight"),
                  self._slice(dflat, pre + "conv1.bias"), F(n_ws), n_ws, dt)
             return dx.view(B, h, w, c), None
-        self._wgrad(dt1, 2 * c, AM_PLAIN, S["n1"], c, AM_PLAIN, None, 1, M, 2 * c, c, 0, 0, 0, 0,
+        self._wgrad(run, dt1, 2 * c, AM_PLAIN, S["n1"], c, AM_PLAIN, None, 1, M, 2 * c, c, 0, 0, 0, 0,
                     self._slice(dflat, pre + "conv1.weight"), self._slice(dflat, pre + "conv1.bias"))
-        pend = dict(pre=pre, geo=geo, dt1=dt1, x=S["x"].reshape(M, c), st1=S["st1"], dy=dy)
+        pend = dict(pre=pre, geo=geo, ln_epilogue=plan.ln_epilogue, dt1=dt1, x=S["x"].reshape(M, c), st1=S["st1"], dy=dy)
         if defer:
             return None, pend
-        return self._conv1_bwd(P, Wt, dflat, **pend), None
+        return self._conv1_bwd(P, run, dflat, **pend), None
 
-    def _conv1_bwd(self, P, Wt, dflat, pre, geo, dt1, x, st1, dy):
+    def _conv1_bwd(self, P, run: _Run, dflat, pre, geo, ln_epilogue, dt1, x, st1, dy):
         """conv1 input gradient + norm1 backward + the residual dy: a block's dx."""
         B, h, w, c = geo
         M = B * h * w
         dt = self.dt
         dx = torch.empty(M, c, device=dt1.device, dtype=self.adt)
-        # LN backward in the conv1 dgrad's epilogue (dn1 never stored) at these widths
-        if dt != 0 and c in (32, 64, 128, 256):
-            self._dgrad_ln(Wt, dflat, P, pre, "conv1.weight", "norm1", dt1, x, st1, dy, dx, M, c)
+        if ln_epilogue:  # LN backward in the conv1 dgrad's epilogue (dn1 never stored)
+            self._dgrad_ln(run, dflat, P, pre, "conv1.weight", "norm1", dt1, x, st1, dy, dx, M, c)
         else:
             dn1 = torch.empty(M, c, device=dt1.device, dtype=self.adt)
-            self._mm(Wt, dt1, 2 * c, AM_PLAIN, None, 1, pre + "conv1.weight", dn1, c, CM_PLAIN, M, c, 2 * c,
+            self._mm(run.w, dt1, 2 * c, AM_PLAIN, None, 1, pre + "conv1.weight", dn1, c, CM_PLAIN, M, c, 2 * c,
                      dgrad=True)
             lg = query("ln_nhwc_grid", M, c, dt)
-            sw, sb = self._ws(lg * c, dt1.device), self._ws(lg * c, dt1.device)
+            sw, sb = self._ws(run, lg * c, dt1.device), self._ws(run, lg * c, dt1.device)
             call("ln_bwd_nhwc", dn1, x, st1, self._slice(P, pre + "norm1.weight"), dy, dx, sw, sb, M, c, dt)
             self._reduce(sw, lg, c, self._slice(dflat, pre + "norm1.weight"))
             self._reduce(sb, lg, c, self._slice(dflat, pre + "norm1.bias"))
         return dx.view(B, h, w, c)
 
-    def _dgrad_ln(self, Wt, dflat, P, pre, wkey, norm, dt, x, st, dres, out, M, c):
-        """dn = dt . W (bf16 transposed weight copy) and the LayerNorm2d backward + residual in one launch
+    def _dgrad_ln(self, run: _Run, dflat, P, pre, wkey, norm, dt, x, st, dres, out, M, c):
+        """dn = dt . W (16-bit transposed weight copy) and the LayerNorm2d backward + residual in one launch
         (nbp_dgrad_ln_bwd); the LN weight / bias gradients are slab-reduced with the stage's deferred reductions."""
         n_ws = query("dgrad_ln_workspace_floats", M, c)
-        ws = self._ws(n_ws, dt.device)
-        call("dgrad_ln_bwd", dt, 2 * c, self._slice(Wt[2], pre + wkey), 2 * c, M, c, 2 * c, x, st,
+        ws = self._ws(run, n_ws, dt.device)
+        call("dgrad_ln_bwd", dt, 2 * c, self._slice(run.w.ht, pre + wkey), 2 * c, M, c, 2 * c, x, st,
              self._slice(P, pre + norm + ".weight"), dres, out, self._slice(dflat, pre + norm + ".weight"),
              self._slice(dflat, pre + norm + ".bias"), ws, n_ws, self.dt)
 
@@ -1159,8 +1172,6 @@ class NAFNetLocal(NAFNet):
         forward of the view resolves it anew, nothing is cached) and fusion switches."""
         view = cls.__new__(cls)
         view.__dict__.update(net.__dict__)  # shallow: _parameters is net's own dict, flat the same Parameter
-        view._ln_carry = None
-        view._keep = None
         view._active = None
         view._set_train_size(train_size)
         return view
