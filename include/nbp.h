@@ -621,6 +621,30 @@ int nbp_sid_to_float(const void* short_u16, const void* long_u16, const float* r
 int nbp_sid_crop_to_float(const void* const* frames, const int* frame_hw, const int* desc, const float* ratio, int B,
                           int F, int h, int w, float* lq, float* short_raw, float* long_raw, nbp_stream_t s);
 
+/* ------------------------------------------------------------------ image output (imgout.hip, png_write.cpp)
+ * The reference turns a restored tensor into a file with tensor2img + cv2.imwrite
+ * (NAFNet_base/basicsr/utils/img_util.py:42-104,147-163).  Here the frame is quantised and PNG-filtered on the
+ * device, one byte per sample crosses to the host, and the host deflates.
+ *
+ * nbp_img_quantize: src float32 [C][H][W] (C = 1 or 3, 4-byte aligned) -> dst uint8 [H][W][C]; dst channel c is src
+ * channel (reverse ? C-1-c : c).  tensor2img's arithmetic in float32, every operation rounded on its own:
+ * t = min(max(x, lo), hi); t = (t - lo) / (hi - lo) (IEEE division); v = rint(t * 255) (half to even); NaN -> 0.
+ * NBP_ERR_ARG for C not in {1, 3}, H or W < 1, or hi <= lo. */
+int nbp_img_quantize(const float* src, void* dst, int C, int H, int W, float lo, float hi, int reverse,
+                     nbp_stream_t s);
+/* nbp_png_filter: img uint8 [H][W][C] (C = 1 or 3) -> out uint8 [H][1 + W*C], each row the PNG filter-type byte and
+ * the filtered scanline (filters 0-4, bpp = C).  A row takes the type with the least sum of min(b, 256 - b) over its
+ * filtered bytes (the specification's minimum-sum-of-absolute-differences heuristic), ties to the lowest type: the
+ * output is a function of the input alone.  No workspace.  W * C <= 2^24. */
+int nbp_png_filter(const void* img, void* out, int H, int W, int C, nbp_stream_t s);
+/* Host (no GPU, no stream).  nbp_png_encode: the filter kernel's output (on the host) -> a complete 8-bit PNG of
+ * colour type 0 (C = 1) or 2 (C = 3) in out[0, *len); at most `cap` bytes are written and nbp_png_encode_bound(H, W,
+ * C) is always enough (< 0: bad arguments).  Deflate (level 0-9) runs on up to `nthreads` threads over stripes of
+ * whole rows whose size depends on the row length alone, so the file's bytes are the same for every nthreads. */
+long nbp_png_encode_bound(int H, int W, int C);
+int nbp_png_encode(const void* scanlines, int H, int W, int C, int level, int nthreads, void* out, long cap,
+                   long* len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,13 +7,14 @@ reference's Python API (RUA1027/Lowlight_Image_Enhancement: NewBP_model.*, metri
     from lowlight_image_enhancement_amd.metrics.phys_consistency import phys_cons_srgb
 
 `install_aliases()` registers the reference's module names (NewBP_model.*, metrics.{phys_consistency, linear, psnr,
-ssim, color_error, lpips_metric}, basicsr.metrics.lowlight_metrics)
+ssim, color_error, lpips_metric}, basicsr.metrics.lowlight_metrics, basicsr.utils.img_util)
 so unmodified train/eval scripts import this implementation.
 """
 import sys
 
 __version__ = "0.1.0"
-__all__ = ["NAFNet", "NAFNetLocal", "grid_plan", "tiled_forward", "val_forward", "Validator", "install_aliases"]
+__all__ = ["NAFNet", "NAFNetLocal", "grid_plan", "tiled_forward", "val_forward", "Validator", "tensor2img", "imwrite",
+           "ImageWriter", "install_aliases"]
 
 
 def __getattr__(name):  # the networks, imported on first use (importing the package alone stays free of torch)
@@ -26,6 +27,9 @@ def __getattr__(name):  # the networks, imported on first use (importing the pac
     if name == "Validator":  # the device-resident validation pass (opt['val'])
         from . import validation
         return validation.Validator
+    if name in ("tensor2img", "imwrite", "ImageWriter"):  # restored tensors as PNG files
+        from . import imgout
+        return getattr(imgout, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -50,3 +54,5 @@ def install_aliases():
     sys.modules.setdefault("basicsr.data.prefetch_dataloader", prefetch_dataloader)
     sys.modules.setdefault("basicsr.data.data_sampler", data_sampler)
     sys.modules.setdefault("basicsr.utils.file_client", file_client)
+    from . import imgout
+    sys.modules.setdefault("basicsr.utils.img_util", imgout)

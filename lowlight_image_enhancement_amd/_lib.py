@@ -37,7 +37,7 @@ def parse_header(path: str = HEADER) -> Dict[str, Tuple[str, List[str]]]:
     text = open(path).read()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     out = {}
-    for m in re.finditer(r"(const char\*|int|size_t|void)\s+(nbp_\w+)\s*\(([^)]*)\)\s*;", text):
+    for m in re.finditer(r"(const char\*|int|long|size_t|void)\s+(nbp_\w+)\s*\(([^)]*)\)\s*;", text):
         ret, name, args = m.group(1), m.group(2), m.group(3).strip()
         types = []
         if args and args != "void":
@@ -63,7 +63,7 @@ class _Lib:
         for name, (ret, types) in self.sigs.items():
             fn = getattr(self.dll, name)  # AttributeError = header/library mismatch, loud by design
             fn.argtypes = [ctypes.c_void_p if t == "ptr" else _C_TYPES[t] for t in types]
-            fn.restype = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p,
+            fn.restype = {"int": ctypes.c_int, "long": ctypes.c_long, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p,
                           "void": None}[ret]
         if self.dll.nbp_version() != 1:
             raise ImportError("liblowlight_nbp.so version mismatch")

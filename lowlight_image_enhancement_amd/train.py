@@ -393,7 +393,10 @@ class NBPTrainer:
             dst.copy_(src)
         if not self.dp:
             self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
+            # with a live process group its watchdog thread may query events during the capture, as on the segmented
+            # path below: then only this thread's calls are checked (without one nothing changes)
+            have_pg = dist.is_available() and dist.is_initialized()
+            with torch.cuda.graph(self._graph, capture_error_mode="thread_local" if have_pg else "global"):
                 self._graph_out = self._graph_body()
             return
         # data parallel: segments of fwd + bwd cut at every bucket flush (no collective inside any graph), then the

@@ -12,13 +12,14 @@ their kernels directly (nbp_psnr, nbp_ssim_linear with a cached window), the col
 """
 from __future__ import annotations
 
+import os
 from collections import OrderedDict
 from typing import Callable, Dict, Mapping, Optional, Tuple
 
 import torch
 from torch import Tensor
 
-__all__ = ["Validator", "register_metric", "SUPPORTED_METRICS"]
+__all__ = ["Validator", "register_metric", "SUPPORTED_METRICS", "image_name", "save_paths"]
 
 SUPPORTED_METRICS = ("linear_psnr", "linear_ssim", "lpips_distance", "deltae2000_mean", "deltae2000_p95",
                      "edge_deltae2000_mean")
@@ -80,20 +81,45 @@ def _ssim(pred: Tensor, gt: Tensor, data_range: float) -> Tensor:
     return out.view(N, C).mean(dim=1).mean()
 
 
+def image_name(data: Mapping) -> str:
+    """The reference's img_name of a loader item: the basename of its `lq_path` (a str, or the one-element list a
+    DataLoader of batch size 1 makes of it) without the extension."""
+    p = data.get("lq_path") if hasattr(data, "get") else None
+    if isinstance(p, (list, tuple)):
+        if len(p) != 1:
+            raise ValueError(f"lq_path names {len(p)} files; images are saved one item at a time")
+        p = p[0]
+    if not isinstance(p, (str, os.PathLike)):
+        raise ValueError("saving images needs every item's 'lq_path' (a str or a one-element list): it names the files")
+    return os.path.splitext(os.path.basename(os.fspath(p)))[0]
+
+
+def save_paths(save_dir: str, img_name: str, dataset_name: str = "val", current_iter=None) -> Tuple[str, str]:
+    """Where the reference writes an item's restored frame and its ground truth (image_restoration_model.py:498-506):
+    {save_dir}/{dataset_name}/{img_name}.png and ..._gt.png when testing (current_iter None), and
+    {save_dir}/{img_name}/{img_name}_{current_iter}.png and ..._gt.png while training."""
+    if current_iter is None:
+        stem = os.path.join(save_dir, dataset_name, img_name)
+    else:
+        stem = os.path.join(save_dir, img_name, f"{img_name}_{current_iter}")
+    return stem + ".png", stem + "_gt.png"
+
+
 class Validator:
     """Accumulates the metrics of the reference's opt['val'] over a validation set, on the device.
 
     val_opt: `metrics: {name: {type: <one of SUPPORTED_METRICS>, **kwargs}}` with the keyword arguments of
     basicsr.metrics.lowlight_metrics (data_range; net, device; whitepoint; q), and the keys val_forward reads (grids,
-    crop_size_h / crop_size_w or their _ratio forms, max_minibatch).  `use_image` / `save_img` (the uint8 image path and
-    image saving) are not implemented."""
+    crop_size_h / crop_size_w or their _ratio forms, max_minibatch).  The keys `use_image` / `save_img` are rejected:
+    the metrics run on the restored tensor, and images are saved by run(save_dir=...)."""
 
     def __init__(self, val_opt: Mapping, *, device=None) -> None:
         self.opt = val_opt
         for key in ("use_image", "save_img"):
             if val_opt.get(key, False):
                 raise NotImplementedError(f"val.{key}: true is not supported: the metrics run on the restored tensor "
-                                          "(use_image: false) and no image is written")
+                                          "(use_image: false); to save the restored frames pass "
+                                          "run(save_dir=...) instead of val.save_img")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
@@ -191,12 +217,19 @@ class Validator:
         return out
 
     # ------------------------------------------------------------------ the pass
-    def run(self, net, loader, *, rank: Optional[int] = None,
-            world_size: Optional[int] = None) -> "OrderedDict[str, float]":
+    def run(self, net, loader, *, rank: Optional[int] = None, world_size: Optional[int] = None,
+            save_dir: Optional[str] = None, dataset_name: str = "val", current_iter=None, rgb2bgr: bool = True,
+            writer=None) -> "OrderedDict[str, float]":
         """One validation pass: for every item of `loader` with idx % world_size == rank (a dict carrying 'lq' / 'gt' or
         'short' / 'long', CPU tensors are moved to the device), val_forward(net, lq, val_opt) under no_grad in eval mode
         (the previous mode is restored), then update(); returns result().  rank / world_size default to
-        torch.distributed's when it is initialised, else 0 / 1."""
+        torch.distributed's when it is initialised, else 0 / 1.
+
+        With `save_dir`, every item's restored frame and ground truth are also written as PNG files at save_paths(
+        save_dir, image_name(item), dataset_name, current_iter) -- the reference's save_img -- through `writer` (an
+        imgout.ImageWriter; by default one made for the pass), which takes the frames off the stream without a host
+        synchronisation; the files are complete when run() returns, and the metrics are those of a pass without
+        saving.  rgb2bgr is the reference's argument of that name (false reverses the channel order of the files)."""
         import torch.distributed as dist
 
         from .tiling import val_forward
@@ -206,6 +239,10 @@ class Validator:
             world_size = (dist.get_world_size() if on else 1) if world_size is None else world_size
         if world_size < 1 or not 0 <= rank < world_size:
             raise ValueError(f"rank {rank} / world_size {world_size}")
+        own_writer = None
+        if save_dir is not None and writer is None:
+            from .imgout import ImageWriter
+            writer = own_writer = ImageWriter()
         self.reset()
         was_training = bool(getattr(net, "training", False))
         if hasattr(net, "eval"):
@@ -216,8 +253,17 @@ class Validator:
                     if idx % world_size != rank:
                         continue
                     lq, gt = self._unpack(data)
-                    self.update(val_forward(net, lq, self.opt), gt)
+                    pred = val_forward(net, lq, self.opt)
+                    self.update(pred, gt)
+                    if save_dir is not None:
+                        img_path, gt_path = save_paths(save_dir, image_name(data), dataset_name, current_iter)
+                        writer.write(pred, img_path, rgb2bgr=rgb2bgr)
+                        writer.write(gt, gt_path, rgb2bgr=rgb2bgr)
+            if save_dir is not None:
+                writer.flush()
         finally:
+            if own_writer is not None:
+                own_writer.close()
             if hasattr(net, "train"):
                 net.train(was_training)
         return self.result()
