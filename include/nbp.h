@@ -645,6 +645,35 @@ long nbp_png_encode_bound(int H, int W, int C);
 int nbp_png_encode(const void* scanlines, int H, int W, int C, int level, int nthreads, void* out, long cap,
                    long* len);
 
+/* ------------------------------------------------------------------ NIQE (niqe.hip)
+ * The reference's no-reference metric calculate_niqe (NAFNet_base/basicsr/metrics/niqe.py, convert_to='y') on the
+ * device, no host synchronisation, every reduction fixed-order.  H x W is the frame after crop_border; the metric
+ * covers its top-left floor(H/96)*96 x floor(W/96)*96 pixels (Hc x Wc), blocks = (Hc/96) * (Wc/96), and a frame
+ * with fewer than one block in either direction is NBP_ERR_ARG.
+ *
+ * nbp_niqe_luma: img = the first pixel of the (cropped) frame, uint8 (is_u8 != 0) or float32 values in [0, 255],
+ * pixel (r, c) channel k at img[r*row_stride + c*pix_stride + k*ch_stride] (strides in elements: any of HWC, CHW, HW
+ * without a copy); channels = 3 (B, G, R) or 1 -> y float32 [Hc][Wc].  Three channels: v = fl32(x/255),
+ * d = b*24.966 + g*128.553 + r*65.481 + 16 in float64, Y = fl32(fl32(d/255) * 255); one channel: Y = fl32(x). */
+int nbp_niqe_luma(const void* img, int is_u8, int H, int W, int channels, long row_stride, long pix_stride,
+                  long ch_stride, float* y, nbp_stream_t s);
+/* nbp_niqe_features: y [Hc][Wc] (nbp_niqe_luma's output) -> feat float64 [blocks][36], row idx_w * (Hc/96) + idx_h,
+ * columns 0-17 of scale 1 (96 x 96 blocks) and 18-35 of scale 2 (48 x 48 blocks of the 2 x 2 pair-mean plane), per
+ * scale alpha, (beta_l + beta_r)/2, then alpha, mean, beta_l, beta_r of the four circular pair products.
+ * window: float64 [49], the correlation weights in raster order (the 7 x 7 Gaussian window, flipped as
+ * scipy.ndimage.convolve flips it), replicated border, float64 sums rounded to float32 where scipy does.
+ * tables: float64 [4][9801] over gam = 0.2 ... 10.000: r_gam = Gamma(2/a)^2 / (Gamma(1/a) Gamma(3/a)) (strictly
+ * increasing), sqrt(Gamma(1/a)/Gamma(3/a)), Gamma(2/a)/Gamma(1/a), gam.  The fit takes np.argmin's index (ties to the
+ * lower one, a NaN ratio -> index 0).  ws: nbp_niqe_workspace_bytes(H, W) bytes (the scale-2 plane). */
+size_t nbp_niqe_workspace_bytes(int H, int W);
+int nbp_niqe_features(const float* y, int H, int W, const double* window, const double* tables, void* ws, double* feat,
+                      nbp_stream_t s);
+/* nbp_niqe_score: feat [rows][36] (1 <= rows <= 16384), mu_pris [36], cov_pris [36][36] float64 -> out [1] =
+ * sqrt(d A^-1 d^T), d = mu_pris - nanmean(feat) per column, A = (cov_pris + cov)/2 with cov the covariance (ddof 1) of
+ * the rows of feat that hold no NaN; A^-1 by a float64 Cholesky solve.  Fewer than two such rows give NaN. */
+int nbp_niqe_score(const double* feat, int rows, const double* mu_pris, const double* cov_pris, double* out,
+                   nbp_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
