@@ -473,6 +473,16 @@ int nbp_rgb_to_lab(const float* rgb, int B, int H, int W, float* lab, nbp_stream
 size_t nbp_psnr_workspace_doubles(int N, long L);
 int nbp_psnr(const float* pred, const float* tgt, int N, long L, double data_range, double eps, int diff_double,
              double* ws, double* mse, double* psnr, nbp_stream_t s);
+/* Channel-wise RGB PSNR and CPSNR (metrics/channelwise.py:111-222, rgb_psnr and cpsnr_rgb) in one pass over pred and
+   tgt, fp32 [N][3][L]: per plane sse = sum (double(p) - double(t))^2, with clamp != 0 both clamped to [0, clamp_hi]
+   first (_clamp_opt, :104-108, after the widening of :146-147); out float64 [N][5] = {PSNR_R, PSNR_G, PSNR_B, their
+   mean, CPSNR}, PSNR = 10 log10(data_range^2 / max(mse, eps)) (:150-154: no inf, identical planes give
+   10 log10(data_range^2 / eps)), CPSNR from the mean of the three MSEs (:209-214).  Chunk partials in ws are added in
+   ascending order by a finish launch: no atomics, the same bits on every run.  3 N <= 65535; 64-bit element offsets.
+   ws: nbp_rgb_psnr_workspace_doubles(N, L) doubles. */
+size_t nbp_rgb_psnr_workspace_doubles(int N, long L);
+int nbp_rgb_psnr(const float* pred, const float* tgt, int N, long L, double data_range, double eps, int clamp,
+                 double clamp_hi, double* ws, double* out, nbp_stream_t s);
 /* calculate_ssim input alignment (metrics/ssim.py): BT.601 luma of NCHW RGB (color_space='y', :119-131) -> [N,1,H,W],
  * and F.interpolate(bilinear / bicubic, align_corners=False) of `planes` Hi x Wi planes to Ho x Wo (resize_policy
  * 'resize', :144-152; torch's CPU source-index and weight formulas). */
@@ -557,6 +567,20 @@ int nbp_lpips_tap_fwd(const void* a, const void* b, const float* w, int N, long 
                       float* out, int dtype, nbp_stream_t s);
 int nbp_lpips_tap_bwd(const void* a, const void* b, const float* w, int N, long HW, int C, const float* up, void* da,
                       int dtype, nbp_stream_t s);
+/* Spatial LPIPS (lpips 0.1.4 LPIPS(spatial=True), as metrics/perceptual.py:86,179-195 asks of it): the value is
+   sum_k nn.Upsample(size=(H, W), mode='bilinear', align_corners=False)(lin_k((u_k - v_k)^2)), [N][1][H][W].
+   nbp_lpips_tap_map: the per-pixel value nbp_lpips_tap_fwd reduces, map[n][p] = sum_c w_c (u_c - v_c)^2 over the
+   N * HW pixels of one tap (a, b: NHWC [N][HW][C] in `dtype`, C a multiple of 8), fp32 [N][HW].
+   nbp_lpips_map_blend: maps = `layers` (1..5) such fp32 maps packed one after the other, layer k [N][h_k][w_k];
+   hw = HOST int [layers][2] = {h_k, w_k} (read during the call; all sizes within [1, 16384]).  One launch, every pixel
+   of out [N][H][W] written once: +0.0f plus, in ascending layer order, the layer's bilinear value at integer-exact
+   source coordinates: for destination i, num = (2i + 1) h - H; num < 0: i0 = 0, l = 0; else i0 = num / 2H,
+   l = float(num % 2H) / float(2H); i1 = min(i0 + 1, h - 1); the same in x; value = (1-lh) ((1-lw) v00 + lw v01) +
+   lh ((1-lw) v10 + lw v11), each product and sum rounded on its own.  A layer of the output's size passes through
+   bit for bit.  No atomics, no workspace. */
+int nbp_lpips_tap_map(const void* a, const void* b, const float* w, int N, long HW, int C, float* map, int dtype,
+                      nbp_stream_t s);
+int nbp_lpips_map_blend(const float* maps, const int* hw, int layers, int N, int H, int W, float* out, nbp_stream_t s);
 /* d += g * (post > 0) over n bf16 elements (a tapped post-ReLU map's gradient joining the backward walk). */
 int nbp_add_relu_masked(void* d, const void* g, const void* post, long n, int dtype, nbp_stream_t s);
 /* Feature distance over n bf16 elements: out = scale * sum (a-b)^2 (mode 0) or |a-b| (mode 1); the backward writes

@@ -7,7 +7,7 @@ reference's Python API (RUA1027/Lowlight_Image_Enhancement: NewBP_model.*, metri
     from lowlight_image_enhancement_amd.metrics.phys_consistency import phys_cons_srgb
 
 `install_aliases()` registers the reference's module names (NewBP_model.*, metrics.{phys_consistency, linear, psnr,
-ssim, color_error, lpips_metric}, basicsr.metrics.lowlight_metrics, basicsr.utils.img_util)
+ssim, color_error, lpips_metric, channelwise, perceptual}, basicsr.metrics.lowlight_metrics, basicsr.utils.img_util)
 so unmodified train/eval scripts import this implementation.
 """
 import sys
@@ -48,6 +48,9 @@ def install_aliases():
     sys.modules.setdefault("metrics.ssim", ssim)
     sys.modules.setdefault("metrics.color_error", color_error)
     sys.modules.setdefault("metrics.lpips_metric", lpips_metric)
+    from .metrics import channelwise, perceptual
+    sys.modules.setdefault("metrics.channelwise", channelwise)
+    sys.modules.setdefault("metrics.perceptual", perceptual)
     sys.modules.setdefault("basicsr.metrics.lowlight_metrics", lowlight_metrics)
     from .data import data_sampler, file_client, prefetch_dataloader, sony_sid_lmdb_dataset
     sys.modules.setdefault("basicsr.data.sony_sid_lmdb_dataset", sony_sid_lmdb_dataset)

@@ -237,6 +237,95 @@ __global__ __launch_bounds__(256) void lpips_tap_fwd(const HT* __restrict__ a, c
   if (threadIdx.x == 0) slab[(long)n * chunks + blockIdx.x] = t;
 }
 
+// The per-pixel value lpips_tap_fwd reduces, written out: map[p] = sum_c w_c (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2
+// over the N * HW pixels (lpips 0.1.4 spatial=True: the 1x1 `lin` head's output before the upsample).  Same loads,
+// norms and per-lane channel order as the forward; the channel sum closes with a group shuffle in fp32.
+template <int G, int V, typename HT>
+__global__ __launch_bounds__(256) void lpips_tap_map(const HT* __restrict__ a, const HT* __restrict__ b,
+                                                     const float* __restrict__ w, int C, long npix,
+                                                     float* __restrict__ map) {
+  constexpr int GPB = 256 / G;
+  const int lg = threadIdx.x % G, grp = threadIdx.x / G, nch = C / 8;
+  float wr[V][8];
+#pragma unroll
+  for (int j = 0; j < V; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) wr[j][e] = j * G + lg < nch ? w[(j * G + lg) * 8 + e] : 0.f;
+  for (long p = (long)blockIdx.x * GPB + grp; p < npix; p += (long)gridDim.x * GPB) {
+    TapRow<G, V, HT> r;
+    tap_load<G, V, HT>(r, a + p * C, b + p * C, lg, nch);
+    float sa = 0.f, sb = 0.f;
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        sa = fmaf((float)r.a[j][e], (float)r.a[j][e], sa);
+        sb = fmaf((float)r.b[j][e], (float)r.b[j][e], sb);
+      }
+    sa = group_sum<G>(sa);
+    sb = group_sum<G>(sb);
+    const float ia = 1.f / (sqrtf(sa) + 1e-10f), ib = 1.f / (sqrtf(sb) + 1e-10f);
+    float d = 0.f;
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float t = (float)r.a[j][e] * ia - (float)r.b[j][e] * ib;
+        d = fmaf(wr[j][e] * t, t, d);
+      }
+    d = group_sum<G>(d);
+    if (lg == 0) map[p] = d;
+  }
+}
+
+// lpips 0.1.4 spatial=True: out = sum_k nn.Upsample(size=(H, W), mode='bilinear', align_corners=False)(map_k).
+// One thread per output pixel, every pixel written once: +0.0f, then the layers' interpolated values added in
+// ascending layer order.  Source coordinates are integers (exact): for destination i, layer height h, output height H,
+// num = (2i + 1) h - H; num < 0 -> i0 = 0, l = 0; else i0 = num / 2H, l = float(num % 2H) / float(2H);
+// i1 = min(i0 + 1, h - 1) -- torch's src = max(h/H (i + 0.5) - 0.5, 0) in exact arithmetic.  A layer of the output's
+// own size has l = 0 everywhere and passes through bit for bit.  Every product and sum is rounded on its own.
+struct BlendDims {
+  int h[5], w[5];
+  long off[5];  // first element of layer k in the packed buffer
+};
+
+__device__ __forceinline__ void blend_coord(int i, int h, int H, int& i0, int& i1, float& l) {
+  const int num = (2 * i + 1) * h - H;
+  if (num < 0) {
+    i0 = 0;
+    l = 0.f;
+  } else {
+    const int den = 2 * H, q = num / den;
+    i0 = min(q, h - 1);
+    l = (float)(num - q * den) / (float)den;
+  }
+  i1 = min(i0 + 1, h - 1);
+}
+
+__global__ __launch_bounds__(256) void lpips_map_blend(const float* __restrict__ maps, BlendDims dm, int layers, int H,
+                                                       int W, long total, float* __restrict__ out) {
+#pragma clang fp contract(off)
+  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    const int j = (int)(e % W);
+    const long t = e / W;
+    const int i = (int)(t % H);
+    const long n = t / H;
+    float acc = 0.f;
+    for (int k = 0; k < layers; ++k) {
+      const int h = dm.h[k], w = dm.w[k];
+      int i0, i1, j0, j1;
+      float lh, lw;
+      blend_coord(i, h, H, i0, i1, lh);
+      blend_coord(j, w, W, j0, j1, lw);
+      const float* m = maps + dm.off[k] + n * ((long)h * w);
+      const float top = (1.f - lw) * m[(long)i0 * w + j0] + lw * m[(long)i0 * w + j1];
+      const float bot = (1.f - lw) * m[(long)i1 * w + j0] + lw * m[(long)i1 * w + j1];
+      acc = acc + ((1.f - lh) * top + lh * bot);
+    }
+    out[e] = acc;
+  }
+}
+
 __global__ void lpips_finalize(const double* __restrict__ slab, int N, int chunks, double inv_hw, int accumulate,
                                float* __restrict__ out) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -575,6 +664,39 @@ int nbp_lpips_tap_fwd(const void* a, const void* b, const float* w, int N, long 
   });
   lpips_finalize<<<cdiv(N, 256), 256, 0, S(s)>>>(ws, N, chunks, 1.0 / (double)HW, accumulate, out);
   return check_launch("lpips_tap_fwd");
+}
+
+int nbp_lpips_tap_map(const void* a, const void* b, const float* w, int N, long HW, int C, float* map, int dtype,
+                      nbp_stream_t s) {
+  NBP_REQUIRE(a && b && w && map && N > 0 && HW > 0 && C >= 8 && C % 8 == 0 && C <= 2048, "nbp_lpips_tap_map: bad args");
+  const long npix = (long)N * HW;
+  NBP_DISPATCH_ALL(dtype, HT, {
+    const HT* pa = reinterpret_cast<const HT*>(a);
+    const HT* pb = reinterpret_cast<const HT*>(b);
+    const long gpb = 256 / tap_lanes(C / 8);
+    long g = (npix + gpb - 1) / gpb;
+    if (g > 8192) g = 8192;
+    NBP_TAP_DISPATCH(lpips_tap_map, (unsigned)g, pa, pb, w, C, npix, map);
+  });
+  return check_launch("lpips_tap_map");
+}
+
+int nbp_lpips_map_blend(const float* maps, const int* hw, int layers, int N, int H, int W, float* out, nbp_stream_t s) {
+  NBP_REQUIRE(maps && hw && out && layers >= 1 && layers <= 5 && N > 0, "nbp_lpips_map_blend: bad args");
+  NBP_REQUIRE(H > 0 && W > 0 && H <= 16384 && W <= 16384, "nbp_lpips_map_blend: output size within [1, 16384]");
+  BlendDims dm = {};
+  long off = 0;
+  for (int k = 0; k < layers; ++k) {
+    NBP_REQUIRE(hw[2 * k] > 0 && hw[2 * k + 1] > 0 && hw[2 * k] <= 16384 && hw[2 * k + 1] <= 16384,
+                "nbp_lpips_map_blend: layer size within [1, 16384]");
+    dm.h[k] = hw[2 * k];
+    dm.w[k] = hw[2 * k + 1];
+    dm.off[k] = off;
+    off += (long)N * dm.h[k] * dm.w[k];
+  }
+  const long total = (long)N * H * W;
+  lpips_map_blend<<<grid_for(total), 256, 0, S(s)>>>(maps, dm, layers, H, W, total, out);
+  return check_launch("lpips_map_blend");
 }
 
 int nbp_lpips_tap_bwd(const void* a, const void* b, const float* w, int N, long HW, int C, const float* up, void* da,

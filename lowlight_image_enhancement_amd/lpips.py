@@ -235,15 +235,73 @@ class _LPIPSFn(torch.autograd.Function):
         return outs[0], outs[1], None, None, None
 
 
-class LPIPS(nn.Module):
-    """lpips.LPIPS(net='vgg') drop-in: forward(in0, in1, retPerLayer=False, normalize=False) -> [N,1,1,1]."""
+MIN_SIZE = {"vgg": 16, "alex": 31}  # the smallest H and W each trunk reaches its last tap from
 
-    def __init__(self, net: str = "vgg", weights=None, version: str = "0.1", precision: str = "auto", **_):
+
+def tap_sizes(net: str, H: int, W: int):
+    """[(h_k, w_k)] of the five taps for an H x W input: vgg halves (floor) four times; alex is conv 11/4 pad 2, then
+    two 3x3/2 pools without padding (the stride-1 convs keep the size)."""
+    if net == "vgg":
+        return [(H >> k, W >> k) for k in range(5)]
+    c0 = ((H + 4 - 11) // 4 + 1, (W + 4 - 11) // 4 + 1)
+    p1 = ((c0[0] - 3) // 2 + 1, (c0[1] - 3) // 2 + 1)
+    p2 = ((p1[0] - 3) // 2 + 1, (p1[1] - 3) // 2 + 1)
+    return [c0, p1, p2, p2, p2]
+
+
+def _check_geometry(net: str, H: int, W: int) -> None:
+    lo = MIN_SIZE[net]
+    if H < lo or W < lo:
+        why = ("four 2x2 pools must leave a pixel" if net == "vgg" else
+               "the second 3x3/2 max pool needs a 3x3 input (torch's AlexNet raises below it too)")
+        raise ValueError(f"LPIPS(net={net!r}) needs H and W >= {lo}: {why}. Received H={H}, W={W}.")
+
+
+def blend_maps(maps, sizes, N: int, H: int, W: int) -> torch.Tensor:
+    """nbp_lpips_map_blend: `maps` = fp32 layer maps packed in one buffer (layer k [N][h_k][w_k], sizes[k] = (h_k, w_k))
+    -> [N,1,H,W], the layers' bilinear (align_corners=False) values added in ascending order onto +0."""
+    hw = torch.tensor(sizes, dtype=torch.int32).contiguous()  # host table, read during the call
+    out = torch.empty(N, 1, H, W, device=maps.device)
+    call("lpips_map_blend", maps, hw, len(sizes), N, H, W, out)
+    return out
+
+
+def _spatial_maps(stack, lins, t0, t1):
+    """The five per-pixel tap maps (nbp_lpips_tap_map) packed in one fp32 buffer, and their sizes."""
+    N = t0[0].shape[0]
+    sizes = [(int(a.shape[1]), int(a.shape[2])) for a in t0]
+    packed = torch.empty(sum(N * h * w for h, w in sizes), device=t0[0].device)
+    off = 0
+    for k, (h, w) in enumerate(sizes):
+        call("lpips_tap_map", t0[k], t1[k], lins[k], N, h * w, t0[k].shape[3], packed[off:off + N * h * w], stack.dtype)
+        off += N * h * w
+    return packed, sizes
+
+
+class LPIPS(nn.Module):
+    """lpips.LPIPS(net='vgg' | 'alex', spatial=False) drop-in:
+    forward(in0, in1, retPerLayer=False, normalize=False) -> [N,1,1,1], or [N,1,H,W] with spatial=True: the per-pixel
+    map sum_k upsample(lin_k((u_k - v_k)^2), size=(H, W)) (bilinear, align_corners=False; nbp_lpips_tap_map per layer
+    and one nbp_lpips_map_blend).  retPerLayer=True returns (val, [the five per-layer terms]) with val their sum in
+    ascending order, as lpips forms it.  The spatial map and retPerLayer are inference only: an input that requires
+    grad raises (the [N,1,1,1] value alone carries the input gradient).
+
+    Geometry: net='vgg' needs H, W >= 16 (four 2x2 pools), net='alex' H, W >= 31 (its second 3x3/2 pool needs a 3x3
+    input; torch raises there too); smaller inputs raise ValueError.  Not built: net='squeeze' and version != '0.1'
+    (NotImplementedError)."""
+
+    def __init__(self, net: str = "vgg", weights=None, version: str = "0.1", precision: str = "auto",
+                 spatial: bool = False, **_):
         super().__init__()
         if net not in ("vgg", "alex"):
             raise NotImplementedError("LPIPS on MI355X implements net='vgg' (the HybridLossPlus term) and net='alex' "
                                       "(the metric's default)")
+        if version != "0.1":
+            raise NotImplementedError(f"LPIPS on MI355X implements version '0.1' (lpips 0.1.4's default), got "
+                                      f"{version!r}")
         self.net = net
+        self.version = version
+        self.spatial = bool(spatial)
         self._weights = weights
         self._parts = {}
         _vgg.resolve_precision(precision)  # validates
@@ -300,7 +358,53 @@ class LPIPS(nn.Module):
         grads = _tap_distances(stack, lins, t0, t1, out, True, up)
         return _vgg.input_grad(_trunk_backward(stack, tape, grads), in0, SCALE, clamp=clamp)
 
+    @torch.no_grad()
+    def _layers(self, in0, in1, normalize: bool):
+        """(val, [five per-layer terms]) without autograd: [N,1,H,W] each when spatial, else [N,1,1,1]."""
+        _lib.require_cuda(in0, in1)
+        x0, x1 = in0.detach().float(), in1.detach().float()
+        if normalize:  # [0,1] -> [-1,1]
+            x0, x1 = 2 * x0 - 1, 2 * x1 - 1
+        stack, lins = self.parts(in0.device)
+        N, _, H, W = in0.shape
+        t0, _ = _trunk_taps(stack, x0, False)
+        t1, _ = _trunk_taps(stack, x1, False)
+        if self.spatial:
+            packed, sizes = _spatial_maps(stack, lins, t0, t1)
+            val = blend_maps(packed, sizes, N, H, W)
+            return val, (packed, sizes)
+        res = []
+        for k in range(5):
+            a = t0[k]
+            HW = a.shape[1] * a.shape[2]
+            ws = torch.empty(query("lpips_tap_workspace_doubles", N, HW), dtype=torch.float64, device=a.device)
+            out = torch.empty(N, device=a.device)
+            call("lpips_tap_fwd", a, t1[k], lins[k], N, HW, a.shape[3], 0, ws, out, stack.dtype)
+            res.append(out.view(N, 1, 1, 1))
+        val = res[0]
+        for r in res[1:]:
+            val = val + r
+        return val, res
+
     def forward(self, in0, in1, retPerLayer: bool = False, normalize: bool = False):
-        if retPerLayer:
-            raise NotImplementedError("retPerLayer is not supported on MI355X")
-        return _LPIPSFn.apply(in0, in1.to(in0.device), self, bool(normalize), _vgg.resolve_precision(self.precision))
+        in1 = in1.to(in0.device)
+        if in0.shape != in1.shape or in0.dim() != 4 or in0.shape[1] != 3:
+            raise ValueError("LPIPS expects two [N,3,H,W] tensors of the same shape")
+        _check_geometry(self.net, int(in0.shape[2]), int(in0.shape[3]))
+        if not (self.spatial or retPerLayer):
+            return _LPIPSFn.apply(in0, in1, self, bool(normalize), _vgg.resolve_precision(self.precision))
+        if torch.is_grad_enabled() and (in0.requires_grad or in1.requires_grad):
+            raise NotImplementedError("LPIPS: the spatial map and retPerLayer are inference only on MI355X (no gradient "
+                                      "through the per-pixel map); call under torch.no_grad() or detach the inputs")
+        val, extra = self._layers(in0, in1, bool(normalize))
+        if not retPerLayer:
+            return val
+        if self.spatial:  # each layer's own upsampled map: the blend of that layer alone (0 + t_k = t_k)
+            packed, sizes = extra
+            N, _, H, W = in0.shape
+            res, off = [], 0
+            for h, w in sizes:
+                res.append(blend_maps(packed[off:off + N * h * w], [(h, w)], N, H, W))
+                off += N * h * w
+            return val, res
+        return val, extra
