@@ -442,6 +442,34 @@ int nbp_ssim_loss_fwd(const float* x, const float* y, int N, int C, int H, int W
 int nbp_ssim_loss_bwd(const float* x, const float* y, int N, int C, int H, int W, int clamp_in, const float* up,
                       const float* up_map, float* ws, float* gx, nbp_stream_t s);
 
+/* ------------------------------------------------------------------ BasicSR pixel losses (pixel_loss.hip)
+ * cri_pix of pixel_opt (NAFNet_base/basicsr/models/losses/losses.py, loss_util.py) on contiguous NCHW fp32 pred /
+ * target [N][C][HW]; any pointer may be only 4-byte aligned.  One call gives the value and, with want_grad, the
+ * gradient w.r.t. pred from a single pass over the inputs; the losses are even in pred - target, so d/d target is the
+ * same call with pred and target swapped.  No allocation, no host synchronisation.
+ *   kind 0 L1 |d| (sign(0) = 0), 1 MSE d^2, 2 Charbonnier sqrt(d^2 + eps), d = pred - target in fp32
+ *   weight (NULL, weight_channels 0): [N][C][HW] (weight_channels = C) or [N][1][HW] broadcast over C (1)
+ *   reduction 0 'mean': out[0] = loss_weight * sum(elem * w) / n, or with a weight / sum(w) (times C for a one-channel
+ *               weight: loss_util.py:53-58; the denominator is reduced on the device from the weight alone),
+ *             1 'sum': out[0] = loss_weight * sum(elem * w),  2 'none': out[N][C][HW] = loss_weight * elem * w
+ *   up: the upstream gradient in device memory: one float (mean / sum) or a [N][C][HW] map (none); NULL = 1
+ *   grad[N][C][HW] = up * loss_weight * reduction scale * w * d elem / d pred
+ *   ws: nbp_pixel_loss_workspace_doubles(n) doubles, n = N*C*HW (unused with reduction 2).  Sums are float64
+ *   work-group partials combined in index order: repeated calls are bitwise equal. */
+size_t nbp_pixel_loss_workspace_doubles(long n);
+int nbp_pixel_loss(const float* pred, const float* target, const float* weight, int N, int C, long HW,
+                   int weight_channels, int kind, float eps, int reduction, float loss_weight, int want_grad,
+                   const float* up, double* ws, float* out, float* grad, nbp_stream_t s);
+/* PSNRLoss (losses.py:113-138): loss[0] = loss_weight * 10/ln 10 * mean_n log(mse_n + 1e-8), mse_n the mean squared
+ * error of image n over C*HW elements, or with toY (C = 3) over the HW values of the BT.601 luma
+ * ((r*65.481 + g*128.553 + b*24.966) + 16) / 255 in the reference's fp32 order.  Pass 1 writes per-image float64
+ * squared-error partials, a one-work-group kernel the loss and each image's gradient coefficient (up[0], NULL = 1,
+ * folded in), pass 2 (want_grad) grad[N][C][HW] = d loss / d pred; nothing is read back between them.
+ * ws: nbp_psnr_loss_workspace_doubles(N, C, HW, toY) doubles. */
+size_t nbp_psnr_loss_workspace_doubles(int N, int C, long HW, int toY);
+int nbp_psnr_loss(const float* pred, const float* target, int N, int C, long HW, int toY, float loss_weight,
+                  int want_grad, const float* up, double* ws, float* loss, float* grad, nbp_stream_t s);
+
 /* ------------------------------------------------------------------ colour difference (NCHW sRGB [B][3][H][W] fp32) */
 /* DeltaE00Loss (NewBP_model/losses.py:92-143): out[0] = mean over pixels of the loss-form CIEDE2000 between
    rgb_to_lab(clamp01 gen) and rgb_to_lab(clamp01 tgt) (kornia 0.6.12 conversion; clamp = 0 skips the clamps);

@@ -7,8 +7,8 @@ reference's Python API (RUA1027/Lowlight_Image_Enhancement: NewBP_model.*, metri
     from lowlight_image_enhancement_amd.metrics.phys_consistency import phys_cons_srgb
 
 `install_aliases()` registers the reference's module names (NewBP_model.*, metrics.{phys_consistency, linear, psnr,
-ssim, color_error, lpips_metric, channelwise, perceptual}, basicsr.metrics.lowlight_metrics, basicsr.utils.img_util)
-so unmodified train/eval scripts import this implementation.
+ssim, color_error, lpips_metric, channelwise, perceptual}, basicsr.metrics.lowlight_metrics, basicsr.utils.img_util,
+basicsr.models.losses and basicsr.models.losses.losses) so unmodified train/eval scripts import this implementation.
 """
 import sys
 
@@ -59,3 +59,6 @@ def install_aliases():
     sys.modules.setdefault("basicsr.utils.file_client", file_client)
     from . import imgout
     sys.modules.setdefault("basicsr.utils.img_util", imgout)
+    from . import pixel_losses  # the pixel_opt branch: L1Loss, MSELoss, CharbonnierLoss, PSNRLoss, build_loss
+    sys.modules.setdefault("basicsr.models.losses", pixel_losses)
+    sys.modules.setdefault("basicsr.models.losses.losses", pixel_losses)

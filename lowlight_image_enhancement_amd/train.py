@@ -53,7 +53,7 @@ class NBPTrainer:
                  w_deltaE: float = 0.0, w_perc: float = 0.0, w_lpips: float = 0.0, perceptual=None, lpips=None,
                  loss_scale: Optional[str] = "auto", init_scale: float = 2.0 ** 16, growth_factor: float = 2.0,
                  backoff_factor: float = 0.5, growth_interval: int = 2000, lpips_net: str = "vgg",
-                 data_parallel: Optional[bool] = None):
+                 data_parallel: Optional[bool] = None, pixel_loss=None):
         """Loss terms and weights as HybridLossPlus (losses.py:223-372): L1 (raw), Perc (VGG19), LPIPS (vgg), ΔE00,
         SSIM, Phys_srgb; a zero weight skips the term.  `perceptual` / `lpips`: PerceptualLoss / LPIPS modules
         (constructed with the synthetic offline weights when needed and not given; `lpips_net` picks the backbone of
@@ -64,7 +64,14 @@ class NBPTrainer:
         A net left at precision "auto" is resolved here, once (NAFNet.resolved_precision: fp32 outside a CUDA autocast
         region, the region's dtype when the trainer is built inside one); the loss scaler and the VGG / LPIPS trunk type
         follow that value, and every step runs the executor in it whatever region the caller is in by then.  An explicit
-        net.precision is read at every step, as before."""
+        net.precision is read at every step, as before.
+
+        `pixel_loss`: the reference's cri_pix (train.pixel_opt, image_restoration_model.py:57-63,264-269): an L1Loss,
+        MSELoss or CharbonnierLoss of pixel_losses.py with reduction 'mean' or 'sum', or a PSNRLoss; l_pix =
+        cri_pix(out, gt) joins the total with its own loss_weight (value and gradient from one fused launch) and is
+        logged as `l_pix`.  The plain-NAFNet baseline (configs/colab/sid_nafnet_baseline.yml) is
+        NBPTrainer(net, pixel_loss=L1Loss(1.0, 'mean'), w_l1=0, w_phys=0); with pixel_loss and w_l1 == 0 the
+        HybridLossPlus L1 kernels are not launched and `L1_raw` is not logged."""
         self.net = net
         dev = net.flat.device
         self.dev = dev
@@ -72,8 +79,22 @@ class NBPTrainer:
         self.k_shared = int(psf_mode == "mono")
         self.w = (float(w_l1), float(w_ssim), float(w_phys))
         self.w_extra = dict(de=float(w_deltaE), perc=float(w_perc), lpips=float(w_lpips))
+        if pixel_loss is not None:
+            from .pixel_losses import CharbonnierLoss, L1Loss, MSELoss, PSNRLoss
+            if not isinstance(pixel_loss, (L1Loss, MSELoss, CharbonnierLoss, PSNRLoss)):
+                raise TypeError(f"pixel_loss: an L1Loss, MSELoss, CharbonnierLoss or PSNRLoss of pixel_losses, got "
+                                f"{type(pixel_loss).__name__}")
+            if pixel_loss.reduction not in ("mean", "sum"):
+                raise ValueError(f"pixel_loss: reduction {pixel_loss.reduction!r} gives no scalar for the total loss; "
+                                 "use 'mean' or 'sum'")
+        self.pixel_loss = pixel_loss
+        self.n_pix = int(pixel_loss is not None)
+        # l_pix of the last step; its upstream gradient is the LAST entry of up / up_base (after the LPIPS ones), so
+        # the buffers of a trainer without a pixel loss are unchanged
+        self.pix_buf = torch.zeros(1, device=dev) if pixel_loss is not None else None
         # upstream gradients of the loss terms, read by the kernels from device memory: up = up_base * S (the loss
-        # scale), {L1, SSIM, Phys, DeltaE, Perc} then one LPIPS entry per image (d(w * mean_n LPIPS_n) / d LPIPS_n)
+        # scale), {L1, SSIM, Phys, DeltaE, Perc} then one LPIPS entry per image (d(w * mean_n LPIPS_n) / d LPIPS_n),
+        # then 1 for the pixel_loss term when there is one (its loss_weight is folded in by the kernel)
         self.up_base: Optional[torch.Tensor] = None
         self.up: Optional[torch.Tensor] = None
         self._ups: Dict[int, tuple] = {}  # batch size -> (up_base, up), never freed (graphs hold their addresses)
@@ -209,9 +230,17 @@ class NBPTrainer:
         wl1, wss, wph = self.w
         d_out = torch.empty_like(out)
         tmp = torch.empty_like(out)
-        pix_ws = torch.empty(query("pix_workspace_doubles", n), dtype=torch.float64, device=lq.device)
-        call("pix_loss_fwd", out, gt, n, 0, 0.0, 0, 0, pix_ws, self.loss_buf[0:1])
-        call("pix_loss_bwd", out, gt, n, 0, 0.0, 0, 0, self.up[0:1], d_out)
+        # cri_pix alone carries the pixel term when w_l1 == 0: its gradient opens d_out, one launch for both
+        pix_only = self.pixel_loss is not None and wl1 == 0.0
+        if pix_only:
+            self._pixel_term(out, gt, d_out)
+        else:
+            pix_ws = torch.empty(query("pix_workspace_doubles", n), dtype=torch.float64, device=lq.device)
+            call("pix_loss_fwd", out, gt, n, 0, 0.0, 0, 0, pix_ws, self.loss_buf[0:1])
+            call("pix_loss_bwd", out, gt, n, 0, 0.0, 0, 0, self.up[0:1], d_out)
+            if self.pixel_loss is not None:
+                self._pixel_term(out, gt, tmp)
+                call("add", d_out, tmp, d_out, n, 0)
         if wss != 0.0:
             ss_ws = torch.empty(query("ssim_workspace_floats", n), device=lq.device)
             call("ssim_loss_fwd", out, gt, B, C, H, W, 11, 1.0, 1, 1, 0, ss_ws, self.loss_buf[1:2], None)
@@ -250,6 +279,12 @@ class NBPTrainer:
                 self._wait_buckets()
         return out
 
+    def _pixel_term(self, out, gt, grad):
+        """l_pix = cri_pix(out, gt) into pix_buf and its gradient (times the loss scale) into `grad`."""
+        from .pixel_losses import fused_value_and_grad
+        k = self.up.numel() - 1
+        fused_value_and_grad(self.pixel_loss, out, gt, self.up[k:k + 1], self.pix_buf, grad)
+
     def _trunk_dt(self, module) -> Optional[int]:
         return self.vgg_dt if getattr(module, "precision", "auto") == "auto" else None
 
@@ -259,7 +294,7 @@ class NBPTrainer:
         rebound.  Switching to another batch size refreshes that pair's up = up_base * S from the current loss scale
         (a device op: the optimizer of the steps run at other sizes moved S).  The per-image LPIPS value buffer is
         kept per batch size the same way (a captured graph's LPIPS tap kernels write into it)."""
-        if self.up_base is not None and self.up_base.numel() == 5 + B:
+        if self.up_base is not None and self.up_base.numel() == 5 + B + self.n_pix:
             return
         if self.w_extra["lpips"]:
             buf = self._lpips_bufs.get(B)
@@ -270,6 +305,7 @@ class NBPTrainer:
         if pair is None:
             wl1, wss, wph = self.w
             base = [wl1, wss, wph, self.w_extra["de"], self.w_extra["perc"]] + [self.w_extra["lpips"] / B] * B
+            base += [1.0] * self.n_pix
             up_base = torch.tensor(base, dtype=torch.float32, device=self.dev)
             pair = self._ups[B] = (up_base, up_base.clone())
         self.up_base, self.up = pair
@@ -446,6 +482,9 @@ class NBPTrainer:
         lp = self.lpips_buf.mean().view(1) if (wlp and self.lpips_buf is not None) else torch.zeros(1, device=buf.device)
         buf = torch.cat([buf, lp])  # L1, SSIM, Phys, DeltaE, Perc, Total, LPIPS
         buf[5] = wl1 * buf[0] + wss * buf[1] + wph * buf[2] + wde * buf[3] + wpe * buf[4] + wlp * buf[6]
+        if self.pixel_loss is not None:  # l_pix carries its loss_weight already (image_restoration_model.py:264-269)
+            buf = torch.cat([buf, self.pix_buf])
+            buf[5] += buf[7]
         if reduce and self.world > 1:
             dist.all_reduce(buf, group=self.pg)
             buf /= self.world
@@ -454,7 +493,11 @@ class NBPTrainer:
         new_skips, self._skipped_seen = skipped - self._skipped_seen, skipped  # counted once, even when raising below
         if not torch.isfinite(vals).all():
             raise RuntimeError(f"HybridLossPlus detected non-finite values: {vals.tolist()}")
-        out = {"L1_raw": float(vals[0])}
+        out = {}
+        if self.pixel_loss is not None:
+            out["l_pix"] = float(vals[7])
+        if self.pixel_loss is None or wl1:
+            out["L1_raw"] = float(vals[0])
         if wpe:
             out["Perc"] = float(vals[4])
         if wlp:
