@@ -726,6 +726,36 @@ int nbp_niqe_features(const float* y, int H, int W, const double* window, const 
 int nbp_niqe_score(const double* feat, int rows, const double* mu_pris, const double* cov_pris, double* out,
                    nbp_stream_t s);
 
+/* ------------------------------------------------------------------ image-domain PSNR / SSIM (psnr_ssim.hip)
+ * The reference's calculate_psnr and calculate_ssim (NAFNet_base/basicsr/metrics/psnr_ssim.py) on the device, no host
+ * synchronisation, every reduction fixed-order.  img1, img2 = the first pixel of two H x W x C views (after
+ * crop_border), both uint8 (is_u8 != 0) or both float32; pixel (r, c) channel k of image i at
+ * img_i[r*row_stride_i + c*pix_stride_i + k*ch_stride_i] (strides in elements: HWC, CHW, crops and channel slices
+ * without a copy); C = 1 or 3 (B, G, R).  No address outside the views is read.  out: float64 [1].
+ *
+ * nbp_bsr_psnr: mse = float64 mean of (img1 - img2)^2 over H*W*C values; y_channel != 0: over the H*W values of the Y
+ * planes instead (three channels: v = fl32(x/255), d = b*24.966 + g*128.553 + r*65.481 + 16 in float64,
+ * Y = fl32(fl32(d/255) * 255); one channel: Y = fl32(fl32(x/255) * 255)), the difference of two float32 Y values taken
+ * in float64.  max_value = 1 if every value of img1 (of its Y plane when y_channel) is <= 1, else 255 (a NaN gives 255).
+ * out = +inf if mse == 0, else 20 log10(max_value / sqrt(mse)).  ws: nbp_bsr_psnr_workspace_bytes(H, W) bytes. */
+size_t nbp_bsr_psnr_workspace_bytes(int H, int W);
+int nbp_bsr_psnr(const void* img1, const void* img2, int is_u8, int H, int W, int C, long row_stride1,
+                 long pix_stride1, long ch_stride1, long row_stride2, long pix_stride2, long ch_stride2, int y_channel,
+                 void* ws, double* out, nbp_stream_t s);
+/* nbp_bsr_ssim: the mean of the SSIM map ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)) with
+ * mu, s from the 11-tap Gaussian window [11] (float64, sigma 1.5, normalised), filtered separably in float64, the map
+ * evaluated in float64; C1 = (0.01 max_value)^2, C2 = (0.03 max_value)^2.
+ * mode 0 (_ssim_3d): the H x W x C volume, a^2, b^2 and ab rounded to float32, the window applied along rows, columns
+ * and channels with a replicated border of 5 on all three axes; mean over H*W*C; max_value as in nbp_bsr_psnr.
+ * mode 1 (_ssim): per channel, float64 products, only the (H-10) x (W-10) pixels whose window lies inside the view;
+ * mean over (H-10)(W-10)C, NaN when H <= 10 or W <= 10; max_value as in nbp_bsr_psnr.
+ * mode 2 (_ssim_cly): the Y planes (as in nbp_bsr_psnr), float64 products, replicated border, mean over H*W;
+ * max_value 255.  ws: nbp_bsr_ssim_workspace_bytes(H, W, mode) bytes. */
+size_t nbp_bsr_ssim_workspace_bytes(int H, int W, int mode);
+int nbp_bsr_ssim(const void* img1, const void* img2, int is_u8, int H, int W, int C, long row_stride1,
+                 long pix_stride1, long ch_stride1, long row_stride2, long pix_stride2, long ch_stride2, int mode,
+                 const double* window, void* ws, double* out, nbp_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

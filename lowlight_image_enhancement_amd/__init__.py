@@ -7,8 +7,9 @@ reference's Python API (RUA1027/Lowlight_Image_Enhancement: NewBP_model.*, metri
     from lowlight_image_enhancement_amd.metrics.phys_consistency import phys_cons_srgb
 
 `install_aliases()` registers the reference's module names (NewBP_model.*, metrics.{phys_consistency, linear, psnr,
-ssim, color_error, lpips_metric, channelwise, perceptual}, basicsr.metrics.lowlight_metrics, basicsr.utils.img_util,
-basicsr.models.losses and basicsr.models.losses.losses) so unmodified train/eval scripts import this implementation.
+ssim, color_error, lpips_metric, channelwise, perceptual}, basicsr.metrics.{lowlight_metrics, psnr_ssim},
+basicsr.utils.img_util, basicsr.models.losses and basicsr.models.losses.losses) so unmodified train/eval scripts import
+this implementation.
 """
 import sys
 
@@ -52,6 +53,8 @@ def install_aliases():
     sys.modules.setdefault("metrics.channelwise", channelwise)
     sys.modules.setdefault("metrics.perceptual", perceptual)
     sys.modules.setdefault("basicsr.metrics.lowlight_metrics", lowlight_metrics)
+    from .metrics import psnr_ssim  # the image-domain PSNR / SSIM of the `use_image` route
+    sys.modules.setdefault("basicsr.metrics.psnr_ssim", psnr_ssim)
     from .data import data_sampler, file_client, prefetch_dataloader, sony_sid_lmdb_dataset
     sys.modules.setdefault("basicsr.data.sony_sid_lmdb_dataset", sony_sid_lmdb_dataset)
     sys.modules.setdefault("basicsr.data.prefetch_dataloader", prefetch_dataloader)

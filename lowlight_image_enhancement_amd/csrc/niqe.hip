@@ -15,6 +15,7 @@
 // reproducible run to run.
 #include <math.h>
 
+#include "luma.h"
 #include "nbp_common.h"
 
 using namespace nbp;
@@ -35,15 +36,7 @@ constexpr int NQ_FEAT = 18;       // features per scale
 constexpr int NQ_MAX_ROWS = 16384;  // blocks per frame the score stage keeps flags for (a 12288 x 12288 frame)
 
 // ---------------------------------------------------------------- luma
-// v = fl32(x / 255); d = b 24.966 + g 128.553 + r 65.481 + 16 in float64; Y = fl32(fl32(d / 255) * 255).  One channel
-// (layout HW): the reference only casts to float32.
-__device__ __forceinline__ float luma_of(float b, float g, float r) {
-  const float vb = b / 255.0f, vg = g / 255.0f, vr = r / 255.0f;
-  const double d = (((double)vb * 24.966 + (double)vg * 128.553) + (double)vr * 65.481) + 16.0;
-  const float y = (float)(d / 255.0);
-  return y * 255.0f;
-}
-
+// Three channels: luma_of (luma.h).  One channel (layout HW): the reference only casts to float32.
 template <typename T>
 __global__ __launch_bounds__(256) void niqe_luma_kernel(const T* __restrict__ img, int Hc, int Wc, int channels,
                                                         long row_stride, long pix_stride, long ch_stride,
