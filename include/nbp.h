@@ -640,6 +640,24 @@ int nbp_optim_prepare(const float* grad, long n, float grad_scale, float max_nor
    the bias corrections state[3..4]; a no-op when state[2] != 0 (scaler.step's skip). */
 int nbp_adamw_apply(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, const float* state,
                     float beta1, float beta2, float eps, float weight_decay, nbp_stream_t s);
+/* torch.optim.Adam (decoupled 0: L2 decay, g += wd * p before the moments) or AdamW (decoupled 1: p *= 1 - lr * wd)
+   after nbp_optim_prepare, reading state as nbp_adamw_apply does.  A non-null max_exp_avg_sq is amsgrad=True:
+   max = max(max, v) and the denominator is taken from max.  Every buffer 16-byte aligned; a no-op when
+   state[2] != 0.  The hyper-parameters are doubles, torch's Python floats: beta and 1 - beta are each rounded to
+   float32 once, as torch does (formed from a float32 beta, 1 - beta keeps beta's rounding error: 1.3e-5 of
+   1 - 0.999). */
+int nbp_adam_apply(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, long n,
+                   const float* state, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                   nbp_stream_t s);
+/* torch.optim.SGD after nbp_optim_prepare (gradient * state[1], lr = state[5]): g += wd * p; with momentum
+   buf = momentum * buf + (1 - dampening) * g and g = buf (nesterov: g += momentum * buf).  momentum_buf is NULL
+   exactly when momentum == 0.  ctl[3] says whether the buffer is initialised: while it is 0 an applied step copies
+   g into the buffer (torch's first step) and a one-thread launch after the apply sets it; a skipped step
+   (state[2] != 0) changes nothing, ctl[3] included.  Set ctl[3] = 1 after restoring a buffer from a checkpoint.
+   nesterov needs momentum > 0 and dampening == 0.  Every buffer 16-byte aligned.  Hyper-parameters are doubles
+   (1 - dampening is formed before the rounding to float32). */
+int nbp_sgd_apply(float* param, const float* grad, float* momentum_buf, long n, const float* state, int* ctl,
+                  double momentum, double dampening, double weight_decay, int nesterov, nbp_stream_t s);
 
 /* ------------------------------------------------------------------ SID input path
  * Host-side (no GPU, no stream): the reference reads PNG bytes from LMDB (basicsr FileClient 'lmdb',

@@ -8,8 +8,8 @@ reference's Python API (RUA1027/Lowlight_Image_Enhancement: NewBP_model.*, metri
 
 `install_aliases()` registers the reference's module names (NewBP_model.*, metrics.{phys_consistency, linear, psnr,
 ssim, color_error, lpips_metric, channelwise, perceptual}, basicsr.metrics.{lowlight_metrics, psnr_ssim},
-basicsr.utils.img_util, basicsr.models.losses and basicsr.models.losses.losses) so unmodified train/eval scripts import
-this implementation.
+basicsr.utils.img_util, basicsr.models.losses, basicsr.models.losses.losses and basicsr.models.lr_scheduler) so
+unmodified train/eval scripts import this implementation.
 """
 import sys
 
@@ -65,3 +65,5 @@ def install_aliases():
     from . import pixel_losses  # the pixel_opt branch: L1Loss, MSELoss, CharbonnierLoss, PSNRLoss, build_loss
     sys.modules.setdefault("basicsr.models.losses", pixel_losses)
     sys.modules.setdefault("basicsr.models.losses.losses", pixel_losses)
+    from . import lr_scheduler  # setup_schedulers' classes, over one parameter group instead of an optimizer
+    sys.modules.setdefault("basicsr.models.lr_scheduler", lr_scheduler)

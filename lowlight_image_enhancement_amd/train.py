@@ -53,7 +53,7 @@ class NBPTrainer:
                  w_deltaE: float = 0.0, w_perc: float = 0.0, w_lpips: float = 0.0, perceptual=None, lpips=None,
                  loss_scale: Optional[str] = "auto", init_scale: float = 2.0 ** 16, growth_factor: float = 2.0,
                  backoff_factor: float = 0.5, growth_interval: int = 2000, lpips_net: str = "vgg",
-                 data_parallel: Optional[bool] = None, pixel_loss=None):
+                 data_parallel: Optional[bool] = None, pixel_loss=None, optimizer=None, warmup_iter: int = -1):
         """Loss terms and weights as HybridLossPlus (losses.py:223-372): L1 (raw), Perc (VGG19), LPIPS (vgg), ΔE00,
         SSIM, Phys_srgb; a zero weight skips the term.  `perceptual` / `lpips`: PerceptualLoss / LPIPS modules
         (constructed with the synthetic offline weights when needed and not given; `lpips_net` picks the backbone of
@@ -71,7 +71,15 @@ class NBPTrainer:
         cri_pix(out, gt) joins the total with its own loss_weight (value and gradient from one fused launch) and is
         logged as `l_pix`.  The plain-NAFNet baseline (configs/colab/sid_nafnet_baseline.yml) is
         NBPTrainer(net, pixel_loss=L1Loss(1.0, 'mean'), w_l1=0, w_phys=0); with pixel_loss and w_l1 == 0 the
-        HybridLossPlus L1 kernels are not launched and `L1_raw` is not logged."""
+        HybridLossPlus L1 kernels are not launched and `L1_raw` is not logged.
+
+        `optimizer`: the reference's train.optim_g as a spec of optim.py (Adam, AdamW or SGD with torch's keywords);
+        when given, lr / betas / weight_decay / eps come from it.  None is AdamW with the arguments above.  Only the
+        buffers the kind needs exist: exp_avg and exp_avg_sq for Adam / AdamW, max_exp_avg_sq with amsgrad,
+        momentum_buffer for SGD with momentum (nothing for momentum-less SGD); the others are None.  `scheduler`: a
+        TrueCosineAnnealingLR (a function of the iteration) or one of the stateful objects of lr_scheduler.py, told
+        apart by their `update` method; `warmup_iter`: the linear warm-up of base_model.update_learning_rate (-1: none).
+        The lr of each step is computed on the host and uploaded (4 bytes), whatever the kind."""
         self.net = net
         dev = net.flat.device
         self.dev = dev
@@ -108,16 +116,29 @@ class NBPTrainer:
         self.lpips_buf: Optional[torch.Tensor] = None
         self._lpips_bufs: Dict[int, torch.Tensor] = {}  # batch size -> per-image LPIPS values, never freed (as _ups)
         self._skipped_seen = 0  # ctl[2] (skipped steps) at the previous logs() call
+        self.optimizer = optimizer
+        if optimizer is not None:
+            from .optim import _Spec
+            if not isinstance(optimizer, _Spec):
+                raise TypeError(f"optimizer: an Adam, AdamW or SGD spec of optim.py, got {type(optimizer).__name__}")
+            lr, weight_decay = float(optimizer.lr), float(optimizer.weight_decay)
+            if optimizer.kind == "adam":
+                betas, eps = tuple(float(b) for b in optimizer.betas), float(optimizer.eps)
         self.lr, self.betas, self.wd, self.eps = lr, betas, weight_decay, eps
         self.max_norm = max_norm if max_norm is not None else 0.0
         self.scheduler = scheduler
+        self.warmup_iter = int(warmup_iter)
         n = net.numel
         self.grad = torch.zeros(n, device=dev)
-        self.exp_avg = torch.zeros(n, device=dev)
-        self.exp_avg_sq = torch.zeros(n, device=dev)
+        # optimizer state, flat like the parameters; a buffer the kind does not use is None
+        adam = optimizer is None or optimizer.kind == "adam"
+        self.exp_avg = torch.zeros(n, device=dev) if adam else None
+        self.exp_avg_sq = torch.zeros(n, device=dev) if adam else None
+        self.max_exp_avg_sq = torch.zeros(n, device=dev) if adam and optimizer is not None and optimizer.amsgrad else None
+        self.momentum_buffer = torch.zeros(n, device=dev) if not adam and optimizer.momentum != 0 else None
         self.clip_ws = torch.empty(query("clip_workspace_doubles", n), dtype=torch.float64, device=dev)
         # device-side step state (nbp_optim_prepare): state = {norm, grad multiplier, skip, lr/bc1, sqrt(bc2), lr, S},
-        # ctl = {AdamW steps taken, GradScaler growth tracker, skipped steps}
+        # ctl = {steps taken, GradScaler growth tracker, skipped steps, SGD momentum buffer initialised}
         self.opt_state = torch.zeros(8, device=dev)
         self.ctl = torch.zeros(4, dtype=torch.int32, device=dev)
         self._lr_dev = torch.zeros(1, device=dev)
@@ -158,6 +179,31 @@ class NBPTrainer:
         self.comm_events: List[tuple] = []
         if self.dp:
             dist.broadcast(net.flat.data, src=0, group=process_group)
+
+    @classmethod
+    def from_train_opt(cls, net: NAFNet, train_opt: dict, **kw) -> "NBPTrainer":
+        """A trainer from a reference `train:` dict (the caller's dict is not modified): `optim_g` through
+        optim.build_optimizer, `scheduler` (with `total_iter`) through lr_scheduler.build_scheduler, `warmup_iter`
+        (default -1), `use_grad_clip` (default True: max_norm 0.01, else no clip; image_restoration_model.py:308-319)
+        and `pixel_opt` through pixel_losses.build_loss.  A dict with `pixel_opt` and no `hybrid_opt` is the plain
+        baseline: the HybridLossPlus weights w_l1 / w_phys default to 0 then.  Keyword arguments override all of it."""
+        from copy import deepcopy
+
+        from .lr_scheduler import build_scheduler
+        from .optim import build_optimizer
+        opt = deepcopy(dict(train_opt))
+        spec = build_optimizer(opt["optim_g"])
+        args = dict(optimizer=spec, warmup_iter=opt.get("warmup_iter", -1),
+                    max_norm=0.01 if opt.get("use_grad_clip", True) else None)
+        if opt.get("scheduler"):
+            args["scheduler"] = build_scheduler(opt, spec.lr)
+        if opt.get("pixel_opt"):
+            from .pixel_losses import build_loss
+            args["pixel_loss"] = build_loss(opt["pixel_opt"])
+            if not opt.get("hybrid_opt"):
+                args.update(w_l1=0.0, w_phys=0.0)
+        args.update(kw)
+        return cls(net, **args)
 
     # ------------------------------------------------------------------ bucketed all-reduce during backward
     def _on_stage(self, st: Stage):
@@ -321,16 +367,38 @@ class NBPTrainer:
             self.up.copy_(self.up_base)
 
     def _optimizer(self, grad_scale: float):
-        """clip + finiteness verdict + GradScaler update (nbp_optim_prepare), then AdamW (nbp_adamw_apply)."""
+        """clip + finiteness verdict + GradScaler update (nbp_optim_prepare), then the update of the optimizer kind:
+        nbp_adamw_apply (plain AdamW, the default), nbp_adam_apply (Adam, amsgrad) or nbp_sgd_apply."""
         call("optim_prepare", self.grad, self.grad.numel(), float(grad_scale), float(self.max_norm), self.clip_ws,
              self._lr_dev, float(self.betas[0]), float(self.betas[1]), self.opt_state, self.ctl, self.scaler,
              self.up, self.up_base, self.up.numel())
-        call("adamw_apply", self.net.flat.data, self.grad, self.exp_avg, self.exp_avg_sq, self.grad.numel(),
-             self.opt_state, float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd))
+        o = self.optimizer
+        if o is None or (o.kind == "adam" and o.plain_adamw):
+            call("adamw_apply", self.net.flat.data, self.grad, self.exp_avg, self.exp_avg_sq, self.grad.numel(),
+                 self.opt_state, float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.wd))
+        elif o.kind == "adam":
+            call("adam_apply", self.net.flat.data, self.grad, self.exp_avg, self.exp_avg_sq, self.max_exp_avg_sq,
+                 self.grad.numel(), self.opt_state, float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                 float(self.wd), int(o.decoupled))
+        else:
+            call("sgd_apply", self.net.flat.data, self.grad, self.momentum_buffer, self.grad.numel(), self.opt_state,
+                 self.ctl, float(o.momentum), float(o.dampening), float(self.wd), int(bool(o.nesterov)))
+
+    def _opt_buffers(self) -> List[torch.Tensor]:
+        """The optimizer-state buffers this kind has."""
+        return [b for b in (self.exp_avg, self.exp_avg_sq, self.max_exp_avg_sq, self.momentum_buffer) if b is not None]
 
     def _lr_now(self) -> float:
-        """base_model.update_learning_rate (:164-174): iteration i (1-based) runs with the schedule at i - 1."""
-        lr = self.scheduler(self.iter - 1) if self.scheduler is not None else self.lr
+        """base_model.update_learning_rate (:164-186) for iteration self.iter (1-based), called once per iteration:
+        the schedule stands at iter - 1, and while iter < warmup_iter the lr is initial_lr / warmup_iter * iter.  A
+        stateful scheduler (lr_scheduler.py) is stepped here and keeps what the warm-up wrote as its group's lr."""
+        s = self.scheduler
+        if s is not None and hasattr(s, "update"):
+            lr = s.update(self.iter, self.warmup_iter)
+        else:
+            lr = s(self.iter - 1) if s is not None else self.lr
+            if self.iter < self.warmup_iter:
+                lr = self.lr / self.warmup_iter * self.iter
         return struct.unpack("f", struct.pack("f", lr))[0]
 
     @property
@@ -416,7 +484,7 @@ class NBPTrainer:
         self._lr_ev = [None] * 8
         self._ensure_up(ins[0].shape[0])
         # the capture itself must not move any state: snapshot what the side-stream warm-up touches
-        state = [self.net.flat.data, self.exp_avg, self.exp_avg_sq, self.ctl, self.opt_state, self.up] + (
+        state = [self.net.flat.data, *self._opt_buffers(), self.ctl, self.opt_state, self.up] + (
             [self.scaler] if self.scaler is not None else [])
         saved = [x.clone() for x in state]
         side = torch.cuda.Stream()
