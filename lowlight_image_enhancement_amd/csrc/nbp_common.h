@@ -27,6 +27,17 @@ void lt_end(hipStream_t st, const char* name, double flops, double bytes);
 // fp32 implicit-GEMM KH x KW / stride conv over NHWC maps (gemm.hip): mode 0 bias + ReLU, 1 bias, 2 ReLU-mask by R
 int conv_f32(const float* x, int B, int H, int W, int Cin, const float* w, int Cout, int KH, int KW, int stride, int pad,
              const float* bias, int mode, const float* R, float* y, hipStream_t st);
+// gradient-slab reductions (grad_reduce.hip; the queue: grad_queue.h): out[L] = column sums of the [S][L] fp32 slab,
+// queued while this thread defers its reductions (nbp_grad_reduce_defer), launched on st otherwise
+#pragma GCC visibility push(hidden)  // (between two units of the library: not exported)
+class GradQueue;
+void grad_reduce(const float* slab, int S, long L, float* out, hipStream_t st);
+bool grad_reduce_deferred();
+GradQueue& grad_queue();  // this thread's deferred reductions, for a producer that re-plans its queued ones
+// measurement records of this thread's last weight-gradient call (which = 0, 4 values) / group launch (2, 6 values)
+// (wgrad.hip; read by nbp_last_call_stats)
+const double* wgrad_stats(int which);
+#pragma GCC visibility pop
 
 #define NBP_REQUIRE(cond, ...)            \
   do {                                    \

@@ -1,5 +1,5 @@
 """One flush of many deferred gradient reductions (more than one by-value batch: the device descriptor table and ONE
-reduce_table_kernel launch, gemm.hip launch_multi) against the same reductions launched one at a time (immediate mode,
+reduce_table_kernel launch, grad_reduce.hip launch_multi) against the same reductions launched one at a time (immediate mode,
 reduce_multi_kernel with one descriptor): bitwise equal -- every descriptor runs the same reduction code in both -- and
 against a float64 column sum.  The flush also carries layer-scale post-ops whose U / V are reductions of the same flush
 (the table's row descriptors, U / V never written): against float64 (the immediate path reduces U / V with other

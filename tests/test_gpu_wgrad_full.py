@@ -1,4 +1,4 @@
-"""Narrow 16-bit weight gradients on the full-width kernel (wgrad_narrow_full, csrc/gemm.hip) through the C-ABI
+"""Narrow 16-bit weight gradients on the full-width kernel (wgrad_narrow_full, csrc/wgrad.hip) through the C-ABI
 nbp_wgrad_f32: every shape the level-0 / 1 NAFBlocks and down / up convs issue, plus ragged row counts, against a
 float64 reference of dW = G^T X (with the per-image column scale of the SCA operand, NAFNet_arch.py:67) and
 db = colsum G.  The reference computes these gradients with torch autograd over the same operands (NAFNet_arch.py:
