@@ -1,0 +1,373 @@
+"""The NAFNet executor's 16-bit arithmetic restated in plain torch, for per-element bounds on every NAFBlock path.
+
+Test infrastructure only; pure torch, imports on the CPU.  Three runs of one network are compared:
+
+* the oracle: oracle.nafnet.nafnet in float64 (pinned to the reference by tests/test_oracle_golden.py);
+* the emulation: the same network in float64 with a rounding function q applied wherever the executor
+  (lowlight_image_enhancement_amd/nafnet.py, _block_fwd / _block_bwd and the kernels they launch) rounds a value to
+  the 16-bit storage type.  |emulation - oracle| is the error the storage format itself forces on a tensor;
+* the device (tests/test_gpu_block_oracle.py), or on the host a stand-in: the emulation with all arithmetic in float32
+  (correctly rounded float32 operations, so that every host computes the same stand-in).
+
+bound(ref, emu) = 4 * max|emu - ref| + 1e-5 * max|ref| per tensor: four times the format's own error plus the
+project's fp32 gradient tolerance (which carries the tensors the emulation gets exactly, ending.bias for one).
+
+Where the emulation rounds (forward value, and the gradient arriving at it where the executor stores that gradient):
+  intro output; n1, t1, t2, g, h = g (.) a, y, n2, t4, g2 and the block output; the down / up outputs; the weights of
+  every 1x1 conv and of the down / up convs (forward value only: weight gradients are fp32).
+Points that the kernels add to the plain "round every stored tensor" picture (each found by reading the kernel):
+  * SimpleGate, both of a block: the gate is ONE rounding of the fp32 product of the unrounded halves
+    (dwconv.hip dw_sg_pool_fwd `gv = aa * ab`, gemm16_impl.h CM_SG `g[j] = v[2 * j] * v[2 * j + 1]`), while the
+    backward multiplies by the STORED (rounded) t2 / t4 and stores dt2 / dt4 rounded (dwconv.hip sca_sg_bwd; the fused
+    depthwise backward stages dt2 in an LDS tile of the storage type);
+  * the SCA pool sums the unrounded fp32 gate (dw_sg_pool_fwd `pacc += gv`);
+  * h = g (.) a is rounded when conv3's A operand is formed (gemm16_impl.h load8, AM_SCALE:
+    `r[j] = (H)((float)r[j] * s[j])`); its gradient dh is a stored tensor;
+  * conv3 / conv5 input gradients read round16(scale (.) W) (transpose_bf16_kernel: `q.x * sc` before the
+    conversion), not scale (.) round16(W); the layer-scale gradient reads the fp32 weight (nbp_layer_scale_grad gets
+    the slice of P), not the rounded one the forward multiplied by;
+  * dg, dg2 never reach memory (formed in registers from dh / inside the dgrad epilogue), dn1 / dn2 only at the widths
+    without a LayerNorm epilogue (C not in 32 / 64 / 128 / 256): their gradients are left unrounded accordingly;
+  * the intro and ending convs read fp32 weights and fp32 images (conv3x3.hip): nothing rounded but intro's output
+    and ending's input gradient.
+"""
+from __future__ import annotations
+
+import os
+import sys
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+import torch
+import torch.nn.functional as F
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+for _p in (os.path.dirname(_HERE), os.path.join(_HERE, "golden")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+from oracle import nafnet as O  # noqa: E402
+from param_recipe import recipe_state  # noqa: E402
+
+STORAGE = {"bf16": torch.bfloat16, "fp16": torch.float16}
+LN_EPILOGUE_WIDTHS = (32, 64, 128, 256)  # NAFNet._plan_block: ln_epilogue
+FLOOR = 1e-5
+FACTOR = 4.0
+
+
+# ---------------------------------------------------------------------------------------------- rounding
+_JITTER: Optional[torch.Generator] = None  # run_case(jitter=...): another realisation of every rounding decision
+
+
+def _rnd(t: torch.Tensor, st: Optional[torch.dtype], jitter: bool = True) -> torch.Tensor:
+    """t rounded to st.  jitter=False: a weight -- the device rounds the same fp32 weight exactly as the emulation does,
+    so a realisation must not move it (one moved weight is a full ulp on every pixel, an error nothing averages out)."""
+    if st is None:
+        return t
+    if jitter and _JITTER is not None and st != torch.float32:  # 1 / 16 of the storage type's ulp: moves the ties, adds no error of note
+        rel = 2.0 ** -12 if st == torch.bfloat16 else 2.0 ** -15
+        t = t * (1 + rel * torch.randn(t.shape, generator=_JITTER, dtype=t.dtype))
+    return t.to(st).to(t.dtype)
+
+
+class _Round(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, st, grad, jitter=True):
+        ctx.st = st if grad else None
+        return _rnd(x, st, jitter)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _rnd(g, ctx.st), None, None, None
+
+
+def make_q(storage: Optional[torch.dtype]) -> Callable:
+    """q(t, grad=True): t rounded to `storage` in t's own dtype, and (grad=True) the gradient arriving at it rounded
+    too.  storage None: the identity."""
+    if storage is None:
+        q = lambda t, grad=True: t  # noqa: E731
+        q.weight = lambda t: t
+        return q
+
+    def q(t, grad=True):
+        return _Round.apply(t, storage, grad)
+    q.storage = storage
+    q.weight = lambda t: _Round.apply(t, storage, False, False)  # a weight: forward value only, never jittered
+    return q
+
+
+class _Gate(torch.autograd.Function):
+    """SimpleGate as the kernels compute it: forward the product of the unrounded halves (the caller rounds it once);
+    backward against the stored halves, the result stored."""
+
+    @staticmethod
+    def forward(ctx, t, st):
+        c = t.shape[1] // 2
+        ctx.st = st
+        ctx.save_for_backward(_rnd(t, st))
+        return t[:, :c] * t[:, c:]
+
+    @staticmethod
+    def backward(ctx, dg):
+        (ts,) = ctx.saved_tensors
+        c = ts.shape[1] // 2
+        return _rnd(torch.cat([dg * ts[:, c:], dg * ts[:, :c]], 1), ctx.st), None
+
+
+class _ScaledConv(torch.autograd.Function):
+    """r + s (.) (W16 h + b), conv3 / conv5 with their layer scale: the forward multiplies by the rounded weight, the
+    input gradient by round16(s (.) W), dW = s (.) U, db = s (.) V, ds = rowsum(W (.) U) + b (.) V on the fp32 W."""
+
+    @staticmethod
+    def forward(ctx, h, r, W, b, s, st):
+        ctx.st = st
+        ctx.save_for_backward(h, W, b, s)
+        return r + s * F.conv2d(h, _rnd(W, st, False), b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        h, W, b, s = ctx.saved_tensors
+        c = W.shape[0]
+        Ws = _rnd(s.reshape(c, 1, 1, 1) * W, ctx.st, False)
+        dh = F.conv_transpose2d(dy, Ws)
+        U = torch.einsum("bohw,bihw->oi", dy, h)
+        V = dy.sum((0, 2, 3))
+        sv = s.reshape(c)
+        dW = (sv[:, None] * U).reshape(W.shape)
+        ds = ((W.reshape(c, -1) * U).sum(1) + b * V).reshape(s.shape)
+        return dh, dy, dW, sv * V, ds, None
+
+
+# ---------------------------------------------------------------------------------------------- the network
+MUTATIONS = ("tap", "sca", "pair")
+
+
+def emulated_block(P, pre, inp, q, mutation=None, p=lambda t: t):
+    """One NAFBlock as the executor computes it.  mutation (host test only): one deliberate error of the kind a
+    kernel or its launch could make, "tap" / "sca" / "pair".  p: applied to every operation's result (the stand-in's
+    float32 rounding; the identity in the emulation)."""
+    st = getattr(q, "storage", None)
+    c = inp.shape[1]
+    ln_ep = c in LN_EPILOGUE_WIDTHS
+    n1 = q(p(O.layer_norm2d(inp, P[pre + "norm1.weight"], P[pre + "norm1.bias"])), grad=not ln_ep)
+    t1 = q(p(F.conv2d(n1, q.weight(P[pre + "conv1.weight"]), P[pre + "conv1.bias"])))
+    t2 = p(F.conv2d(t1, P[pre + "conv2.weight"], P[pre + "conv2.bias"], padding=1, groups=2 * c))
+    if mutation == "tap":  # pixel (0, 0) misses its (+1, +1) neighbour
+        fix = torch.zeros_like(t2)
+        fix[:, :, 0, 0] = P[pre + "conv2.weight"][:, 0, 2, 2] * t1[:, :, 1, 1]
+        t2 = p(t2 - fix)
+    gf = p(_Gate.apply(t2, st))
+    a = p(F.conv2d(p(F.adaptive_avg_pool2d(gf, 1)), P[pre + "sca.1.weight"], P[pre + "sca.1.bias"]))
+    if mutation == "sca":  # image 0's scale on every image
+        a = a[:1].expand_as(a)
+    h = q(p(q(gf, grad=False) * a))
+    y = q(p(_ScaledConv.apply(h, inp, P[pre + "conv3.weight"], P[pre + "conv3.bias"], P[pre + "beta"], st)))
+    n2 = q(p(O.layer_norm2d(y, P[pre + "norm2.weight"], P[pre + "norm2.bias"])), grad=not ln_ep)
+    t4 = p(F.conv2d(n2, q.weight(P[pre + "conv4.weight"]), P[pre + "conv4.bias"]))
+    if mutation == "pair":  # channels c and c + 1 (the gate partners of 0 and 1) swapped
+        idx = torch.arange(2 * c)
+        idx[c], idx[c + 1] = c + 1, c
+        t4 = t4[:, idx]
+    g2 = q(p(_Gate.apply(t4, st)), grad=False)
+    return q(p(_ScaledConv.apply(g2, y, P[pre + "conv5.weight"], P[pre + "conv5.bias"], P[pre + "gamma"], st)))
+
+
+def emulated_nafnet(P: Dict[str, torch.Tensor], inp: torch.Tensor, enc: Sequence[int], mid: int, dec: Sequence[int],
+                    q: Callable, mutate: Optional[Tuple[str, str]] = None, p: Callable = lambda t: t) -> torch.Tensor:
+    """oracle.nafnet.nafnet with q at the executor's rounding points (module docstring).  mutate = (block prefix,
+    mutation) plants one error in that block; p as in emulated_block."""
+    def block(pre, x):
+        return emulated_block(P, pre, x, q, mutate[1] if mutate and mutate[0] == pre else None, p)
+
+    B, C, H, W = inp.shape
+    pad = 2 ** len(enc)
+    ph, pw = (pad - H % pad) % pad, (pad - W % pad) % pad
+    inp = F.pad(inp, (0, pw, 0, ph))
+    x = q(p(F.conv2d(inp, P["intro.weight"], P["intro.bias"], padding=1)))
+    encs: List[torch.Tensor] = []
+    for i, n in enumerate(enc):
+        for j in range(n):
+            x = block(f"encoders.{i}.{j}.", x)
+        encs.append(x)
+        x = q(p(F.conv2d(x, q.weight(P[f"downs.{i}.weight"]), P[f"downs.{i}.bias"], stride=2)))
+    for j in range(mid):
+        x = block(f"middle_blks.{j}.", x)
+    for i, n in enumerate(dec):
+        x = q(p(F.pixel_shuffle(F.conv2d(x, q.weight(P[f"ups.{i}.0.weight"])), 2) + encs[::-1][i]))
+        for j in range(n):
+            x = block(f"decoders.{i}.{j}.", x)
+    x = p(F.conv2d(x, P["ending.weight"], P["ending.bias"], padding=1))
+    x = p(x + inp)
+    return x[:, :, :H, :W]
+
+
+# ---------------------------------------------------------------------------------------------- the case table
+class Case(NamedTuple):
+    name: str
+    ctor: dict  # NAFNet constructor arguments
+    shape: Tuple[int, int, int]  # B, H, W of the input image
+    switches: dict  # executor attributes set before the forward
+    plan: dict  # {"all" | "first" | "inner" | "last" | block prefix: {BlockPlan field: value}}
+    seed: int = 0  # of the parameters, the image and the upstream gradient
+
+
+def _flat(c, **kw):
+    return dict(img_channel=3, width=c, middle_blk_num=3, enc_blk_nums=[], dec_blk_nums=[], **kw)
+
+
+_CARRY = {"first": dict(carry_next=True), "inner": dict(carry_next=True), "last": dict(carry_next=False)}
+_NO_CARRY = {"all": dict(carry_next=False)}
+_L0 = dict(tile=True, c1dw=False, ln_epilogue=True, ln_fwd=True, drop_t4=True, ffn=True, rows_ffn=False, sg_rc_wg=True,
+           ln_wg=True, sca_fold=True, grouped=False, chandot=False)
+_L1 = dict(tile=True, c1dw=False, ln_epilogue=True, ln_fwd=True, drop_t4=False, ffn=False, rows_ffn=False,
+           sg_rc_wg=False, ln_wg=False, sca_fold=True, grouped=False, chandot=False)
+_ROWS = dict(tile=False, rows_ffn=True, drop_t4=False, ffn=False, grouped=True, sca_fold=True, ln_wg=False,
+             rows_pre=True)
+_PLAIN = dict(tile=False, c1dw=False, ln_epilogue=False, ln_fwd=False, drop_t4=False, ffn=False, rows_ffn=False,
+              sg_rc_wg=False, ln_wg=False, chandot=False)
+
+CASES: List[Case] = [
+    Case("c32", _flat(32), (2, 12, 10), {}, {"all": _L0, **_CARRY}),
+    Case("c32_wide", _flat(32), (1, 9, 70), {}, {"all": _L0, **_CARRY}),
+    Case("c32_stored_t4", _flat(32), (2, 12, 10), dict(sg_rc=False),
+         {"all": dict(_L0, drop_t4=False, ffn=False, sg_rc_wg=False), **_CARRY}),
+    Case("c64", _flat(64), (2, 12, 10), {}, {"all": _L1, **_CARRY}),
+    Case("c64_wide", _flat(64), (1, 9, 70), {}, {"all": _L1, **_CARRY}),
+    Case("c64_stored_tape", _flat(64), (2, 12, 10), dict(fuse_c1dw_tile=False), {"all": dict(_L1, tile=False), **_CARRY}),
+    Case("c128_rows", _flat(128), (2, 8, 8), {},
+         {"all": dict(_ROWS, c1dw=False, ln_epilogue=True, chandot=True), **_CARRY}),
+    Case("c128_launches", _flat(128), (2, 8, 8), dict(fuse_ffn_rows=False),
+         {"all": dict(_ROWS, rows_ffn=False, c1dw=False, ln_epilogue=True, ln_fwd=True, chandot=True), **_CARRY}),
+    Case("c128_hw60", _flat(128), (1, 6, 10), {},
+         {"all": dict(_ROWS, rows_ffn=False, c1dw=False, ln_epilogue=True, ln_fwd=True, chandot=False), **_CARRY}),
+    Case("c256_rows", _flat(256), (2, 8, 8), {},
+         {"all": dict(_ROWS, c1dw=False, ln_epilogue=True, chandot=True), **_CARRY}),
+    Case("c512_c1dw_rows", _flat(512), (2, 16, 16), {},
+         {"all": dict(_ROWS, c1dw=True, chunks=1, ln_epilogue=False, ln_fwd=False), **_CARRY}),
+    Case("c512_rows", _flat(512), (1, 8, 8), {},
+         {"all": dict(_ROWS, c1dw=False, ln_epilogue=False, ln_fwd=False), **_CARRY}),
+    Case("c512_hw60", _flat(512), (1, 6, 10), {},
+         {"all": dict(_PLAIN, grouped=True, sca_fold=True), **_NO_CARRY}),
+    Case("c1024", _flat(1024), (1, 4, 8), {}, {"all": dict(_PLAIN, grouped=True, sca_fold=True), **_NO_CARRY}),
+    Case("c24", _flat(24), (2, 7, 9), {}, {"all": dict(_PLAIN, grouped=False, sca_fold=False), **_NO_CARRY}),
+    Case("c40", _flat(40), (1, 7, 9), {}, {"all": dict(_PLAIN, grouped=False, sca_fold=False), **_NO_CARRY}),
+    Case("c48", _flat(48), (1, 7, 9), {}, {"all": dict(_PLAIN, grouped=False, sca_fold=True), **_NO_CARRY}),
+    Case("c48_sca_unfolded", _flat(48), (1, 7, 9), dict(sca_fold=False),
+         {"all": dict(_PLAIN, grouped=False, sca_fold=False), **_NO_CARRY}),
+    # beyond the folds' own switches: the rebuild without its weight-gradient fold (nbp_dgrad_sg_rc + CM_SG with t4
+    # dropped), conv1's weight gradient as its own launch (nbp_dgrad_ln_bwd at C 32), the tile backward without the SCA fold
+    Case("c32_unfolded", _flat(32), (2, 12, 10), dict(sg_rc_wg=False, ln_wg=False, sca_fold=False),
+         {"all": dict(_L0, ffn=False, sg_rc_wg=False, ln_wg=False, sca_fold=False), **_CARRY}),
+    Case("u32", dict(img_channel=3, width=32, middle_blk_num=1, enc_blk_nums=[1, 1], dec_blk_nums=[1, 1]), (2, 22, 18), {},
+         {"encoders.0.0.": dict(_L0, carry_next=False), "decoders.1.0.": dict(_L0, carry_next=False),
+          "encoders.1.0.": dict(_L1, carry_next=False), "decoders.0.0.": dict(_L1, carry_next=False),
+          "middle_blks.0.": dict(_ROWS, rows_ffn=False, c1dw=False, ln_epilogue=True, ln_fwd=True, chandot=False,
+                                 carry_next=False)}),
+]
+# Seeds.  The factor 4 of the bound is twice the ratio 2 that the float32 stand-in keeps to the emulation's error
+# (test_block_oracle_host.py asserts it for every case and both types).  The emulation is ONE realisation of the
+# rounding decisions and the bound is built on its error, so a case's inputs must be ones on which that realisation is
+# typical: the host test also asserts that further realisations of the stand-in (run_case's jitter) stay within 3 x,
+# three of them per type at the level-less cases and twelve at the U-shaped one.  That case is five blocks deep with
+# two skips and 98 tensors, and its errors have a heavy tail: with inputs chosen on three realisations only, 2 of 24
+# host realisations in bf16 and 1 of 24 in fp16 were themselves over the device bound (up to 1.1 x, at
+# encoders.0.0.sca.1.weight, middle_blks.0.sca.1.bias and middle_blks.0.conv1.bias), and so was the device in bf16
+# (1.16 at encoders.0.0.conv2.bias[35]; 1.61 at encoders.1.0.conv1.bias[5] with inputs chosen on the stand-in ratio
+# alone), while it passed every level-less case at <= 0.65.  Each case takes the first seed of a fixed sequence that
+# meets the host conditions with a little room (stand-in <= 1.9, jittered <= 2.8, u32 <= 2.9 on its 24).  Roughly one
+# seed in five fails the stand-in ratio at a level-less case; at u32 about one seed in a hundred meets all of it.  The
+# choice is made on the host alone.
+_SEEDS = dict(c32=5007, c32_wide=5100, c32_stored_t4=5206, c64=1061, c64_wide=5403, c64_stored_tape=1100,
+              c128_rows=5600, c128_launches=1140, c128_hw60=1160, c256_rows=1180, c512_c1dw_rows=1201, c512_rows=6102,
+              c512_hw60=1240, c1024=6304, c24=6410, c40=6502, c48=6601, c48_sca_unfolded=1340, u32=9007,
+              c32_unfolded=5007)  # c32_unfolded: c32's network and inputs on other launches
+CASES = [c._replace(seed=_SEEDS[c.name]) for c in CASES]
+CASE = {c.name: c for c in CASES}
+
+FP32_CASES: List[Case] = [
+    Case("fp32_c20", _flat(20), (2, 7, 9), {}, {}, 2000),
+    Case("fp32_c32", _flat(32), (2, 12, 10), {}, {}, 2001),
+    Case("fp32_u32", CASE["u32"].ctor, CASE["u32"].shape, {}, {}, 2002),
+]
+
+
+def block_prefixes(ctor: dict) -> List[str]:
+    """The NAFBlocks of a network in forward order."""
+    out = [f"encoders.{i}.{j}." for i, n in enumerate(ctor["enc_blk_nums"]) for j in range(n)]
+    out += [f"middle_blks.{j}." for j in range(ctor["middle_blk_num"])]
+    return out + [f"decoders.{i}.{j}." for i, n in enumerate(ctor["dec_blk_nums"]) for j in range(n)]
+
+
+def expected_plan(case: Case, pre: str) -> dict:
+    """The BlockPlan fields the case asserts for block `pre` (positions are those of a level-less network)."""
+    blocks = block_prefixes(case.ctor)
+    pos = "first" if pre == blocks[0] else ("last" if pre == blocks[-1] else "inner")
+    exp = dict(case.plan.get("all", {}))
+    if not case.ctor["enc_blk_nums"]:
+        exp.update(case.plan.get(pos, {}))
+    exp.update(case.plan.get(pre, {}))
+    return exp
+
+
+def case_inputs(case: Case):
+    """(reference-layout state dict, image, upstream gradient), float32, seeded per case."""
+    k = case.ctor
+    shapes = O.nafnet_param_shapes(k["img_channel"], k["width"], k["middle_blk_num"], k["enc_blk_nums"],
+                                   k["dec_blk_nums"])
+    sd = recipe_state(shapes, case.seed)
+    gen = torch.Generator().manual_seed(case.seed + 7)
+    B, H, W = case.shape
+    x = torch.rand(B, k["img_channel"], H, W, generator=gen)
+    dout = torch.randn(B, k["img_channel"], H, W, generator=gen)
+    return sd, x, dout
+
+
+def run_case(case: Case, dtype: Optional[str], arithmetic: torch.dtype = torch.float64,
+             mutate: Optional[Tuple[str, str]] = None, jitter: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """One forward + backward on the host.  dtype None: the oracle itself; "bf16" / "fp16": the emulation with that
+    storage type.  arithmetic: the dtype everything between the roundings is computed in (float64: the emulation,
+    float32: the host's stand-in for the device).  jitter: a seed; every value is moved by 1 / 16 ulp x N(0, 1)
+    before it is rounded, which gives one more realisation of the rounding decisions (as the device's summation orders
+    do).  Returns float64 {"out", "dx", parameter key: gradient}."""
+    global _JITTER
+    _JITTER = None if jitter is None else torch.Generator().manual_seed(jitter)
+    try:
+        return _run_case(case, dtype, arithmetic, mutate)
+    finally:
+        _JITTER = None
+
+
+def _run_case(case, dtype, arithmetic, mutate):
+    sd, x, dout = case_inputs(case)
+    k = case.ctor
+    assert arithmetic in (torch.float64, torch.float32)
+    P = {n: v.double().requires_grad_(True) for n, v in sd.items()}
+    x = x.double().requires_grad_(True)
+    if dtype is None and mutate is None and arithmetic == torch.float64:
+        out = O.nafnet(P, x, k["enc_blk_nums"], k["middle_blk_num"], k["dec_blk_nums"])
+    else:
+        q = make_q(None if dtype is None else STORAGE[dtype])
+        # float32 arithmetic: every operation in float64, its result (and the gradient arriving at it) rounded to
+        # float32 -- correctly rounded float32 operations, the same on every host (a host's own float32 convolutions
+        # depend on its instruction set: two machines gave errors a factor 2.4 apart on one tensor)
+        p = (lambda t: t) if arithmetic == torch.float64 else (lambda t: _Round.apply(t, torch.float32, True))
+        out = emulated_nafnet(P, x, k["enc_blk_nums"], k["middle_blk_num"], k["dec_blk_nums"], q, mutate, p)
+    out.backward(dout.double())
+    res = {"out": out.detach().double(), "dx": x.grad.double()}
+    res.update({n: v.grad.double() for n, v in P.items()})
+    return res
+
+
+def bound(ref: torch.Tensor, emu: torch.Tensor) -> float:
+    return FACTOR * (emu - ref).abs().max().item() + FLOOR * ref.abs().max().item()
+
+
+def ratios(got: Dict[str, torch.Tensor], ref: Dict[str, torch.Tensor], emu: Dict[str, torch.Tensor]):
+    """[(max|got - ref| / bound, tensor name, index of the worst element)] over every tensor, worst first."""
+    out = []
+    for name, r in ref.items():
+        err = (got[name].double().reshape(r.shape) - r).abs()
+        i = int(err.argmax())
+        out.append((err.reshape(-1)[i].item() / bound(r, emu[name]), name,
+                    tuple(int(v) for v in torch.unravel_index(torch.tensor(i), r.shape))))
+    out.sort(reverse=True)
+    return out
