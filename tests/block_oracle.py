@@ -2,7 +2,9 @@
 
 Test infrastructure only; pure torch, imports on the CPU.  Three runs of one network are compared:
 
-* the oracle: oracle.nafnet.nafnet in float64 (pinned to the reference by tests/test_oracle_golden.py);
+* the oracle: oracle.nafnet.nafnet in float64 (pinned to the reference by tests/test_oracle_golden.py); for
+  NAFNetLocal, local_nafnet below: the same network with every SCA pooling over its TLSC window (pinned to the
+  reference's NAFNetLocal outputs by tests/test_block_oracle_host.py);
 * the emulation: the same network in float64 with a rounding function q applied wherever the executor
   (lowlight_image_enhancement_amd/nafnet.py, _block_fwd / _block_bwd and the kernels they launch) rounds a value to
   the 16-bit storage type.  |emulation - oracle| is the error the storage format itself forces on a tensor;
@@ -30,6 +32,16 @@ Points that the kernels add to the plain "round every stored tensor" picture (ea
     without a LayerNorm epilogue (C not in 32 / 64 / 128 / 256): their gradients are left unrounded accordingly;
   * the intro and ending convs read fp32 weights and fp32 images (conv3x3.hip): nothing rounded but intro's output
     and ending's input gradient.
+The TLSC local window (NAFNetLocal, forward only; csrc/tlsc.hip and NAFNet._local_sca / _block_fwd):
+  * the window sums read the STORED gate (tlsc_colsum loads g from memory, `ldv<T, N>(gp + r * rs, v)`), so the window
+    means come from q(g) -- unlike the global pool above, which sums the unrounded gate;
+  * the column sums, the window means V, a = W V + b (tlsc_sca_a: fp32 MFMA, fp32 weights) and the gather are fp32:
+    nothing rounded;
+  * ga = g (.) a[clamp] is ONE rounding to the storage type of the product of the stored gate and the fp32 a
+    (tlsc_gate `o[n] = (T)(gv[n] * av[n])`);
+  * conv3 then reads ga as it is: AM_PLAIN without a scale (gemm_res_ln, the plain GEMM) or a unit scale
+    (ffn_rows_fwd, `asc = ones`: q(ga * 1) = ga), so nothing is rounded a second time; the pool partials that
+    c1dw_fwd_tile / c1_dw_sg_pool / dw_sg_pool_fwd wrote are not read.
 """
 from __future__ import annotations
 
@@ -139,12 +151,35 @@ class _ScaledConv(torch.autograd.Function):
 
 # ---------------------------------------------------------------------------------------------- the network
 MUTATIONS = ("tap", "sca", "pair")
+LOCAL_MUTATIONS = ("global", "shift", "image")  # of a block that pools over a TLSC window
 
 
-def emulated_block(P, pre, inp, q, mutation=None, p=lambda t: t):
+def local_window(k: Optional[Tuple[int, int]], h: int, w: int) -> Optional[Tuple[int, int]]:
+    """The TLSC window of a block with kernel k on an h x w map (NAFNet._local_window): None where the kernel covers
+    the map (or there is no kernel: the plain NAFNet), the block then pools globally."""
+    if k is None or (k[0] >= h and k[1] >= w):
+        return None
+    return min(h, k[0]), min(w, k[1])
+
+
+def local_pool(x: torch.Tensor, win: Tuple[int, int], shift: int = 0):
+    """test_tlsc_host.tlsc_pool64's arithmetic on an NCHW map: (V, iy, ix) with V the mean of every k1 x k2 window and
+    pooled[i][j] = V[iy[i]][ix[j]], iy = clamp(i - (h - _h) // 2, 0, _h - 1) (the replicate padding).  shift (a planted
+    error): added to both indices before the clamp."""
+    h, w = x.shape[2:]
+    V = F.avg_pool2d(x, win, stride=1)
+    _h, _w = V.shape[2:]
+    assert (_h, _w) == (h - win[0] + 1, w - win[1] + 1)
+    iy = (torch.arange(h) - (h - _h) // 2 + shift).clamp(0, _h - 1)
+    ix = (torch.arange(w) - (w - _w) // 2 + shift).clamp(0, _w - 1)
+    return V, iy, ix
+
+
+def emulated_block(P, pre, inp, q, mutation=None, p=lambda t: t, local=None):
     """One NAFBlock as the executor computes it.  mutation (host test only): one deliberate error of the kind a
-    kernel or its launch could make, "tap" / "sca" / "pair".  p: applied to every operation's result (the stand-in's
-    float32 rounding; the identity in the emulation)."""
+    kernel or its launch could make, "tap" / "sca" / "pair", and at a block with a window "global" / "shift" / "image".
+    p: applied to every operation's result (the stand-in's float32 rounding; the identity in the emulation).  local: the
+    block's TLSC window (k1, k2), None: the SCA pools globally."""
     st = getattr(q, "storage", None)
     c = inp.shape[1]
     ln_ep = c in LN_EPILOGUE_WIDTHS
@@ -156,9 +191,15 @@ def emulated_block(P, pre, inp, q, mutation=None, p=lambda t: t):
         fix[:, :, 0, 0] = P[pre + "conv2.weight"][:, 0, 2, 2] * t1[:, :, 1, 1]
         t2 = p(t2 - fix)
     gf = p(_Gate.apply(t2, st))
-    a = p(F.conv2d(p(F.adaptive_avg_pool2d(gf, 1)), P[pre + "sca.1.weight"], P[pre + "sca.1.bias"]))
-    if mutation == "sca":  # image 0's scale on every image
-        a = a[:1].expand_as(a)
+    if local is None or mutation == "global":  # "global": a block with a window pools over the whole map
+        a = p(F.conv2d(p(F.adaptive_avg_pool2d(gf, 1)), P[pre + "sca.1.weight"], P[pre + "sca.1.bias"]))
+        if mutation == "sca":  # image 0's scale on every image
+            a = a[:1].expand_as(a)
+    else:  # the window means of the STORED gate; V, a and the gather in fp32
+        V, iy, ix = local_pool(q(gf, grad=False), local, shift=1 if mutation == "shift" else 0)
+        a = p(F.conv2d(p(V), P[pre + "sca.1.weight"], P[pre + "sca.1.bias"]))[:, :, iy][:, :, :, ix]
+        if mutation == "image":  # image 0's attention map on every image
+            a = a[:1].expand_as(a)
     h = q(p(q(gf, grad=False) * a))
     y = q(p(_ScaledConv.apply(h, inp, P[pre + "conv3.weight"], P[pre + "conv3.bias"], P[pre + "beta"], st)))
     n2 = q(p(O.layer_norm2d(y, P[pre + "norm2.weight"], P[pre + "norm2.bias"])), grad=not ln_ep)
@@ -172,11 +213,14 @@ def emulated_block(P, pre, inp, q, mutation=None, p=lambda t: t):
 
 
 def emulated_nafnet(P: Dict[str, torch.Tensor], inp: torch.Tensor, enc: Sequence[int], mid: int, dec: Sequence[int],
-                    q: Callable, mutate: Optional[Tuple[str, str]] = None, p: Callable = lambda t: t) -> torch.Tensor:
+                    q: Callable, mutate: Optional[Tuple[str, str]] = None, p: Callable = lambda t: t,
+                    kernels: Optional[Dict[str, Tuple[int, int]]] = None) -> torch.Tensor:
     """oracle.nafnet.nafnet with q at the executor's rounding points (module docstring).  mutate = (block prefix,
-    mutation) plants one error in that block; p as in emulated_block."""
+    mutation) plants one error in that block; p as in emulated_block.  kernels: {block prefix: TLSC kernel size}
+    (NAFNetLocal.local_kernels), None: the plain NAFNet."""
     def block(pre, x):
-        return emulated_block(P, pre, x, q, mutate[1] if mutate and mutate[0] == pre else None, p)
+        local = local_window(kernels[pre], *x.shape[2:]) if kernels else None
+        return emulated_block(P, pre, x, q, mutate[1] if mutate and mutate[0] == pre else None, p, local)
 
     B, C, H, W = inp.shape
     pad = 2 ** len(enc)
@@ -200,6 +244,66 @@ def emulated_nafnet(P: Dict[str, torch.Tensor], inp: torch.Tensor, enc: Sequence
     return x[:, :, :H, :W]
 
 
+# ---------------------------------------------------------------------------------------------- the local oracle
+def local_nafblock(P, pre, inp, k):
+    """oracle.nafnet.nafblock with the SCA's pool over the TLSC window of kernel k (local_arch.py:61-74: the window
+    means, replicate-padded back to the map, then the SCA's 1x1 conv at every pixel).  A kernel that covers the map:
+    the global block."""
+    c = inp.shape[1]
+    win = local_window(k, *inp.shape[2:])
+    if win is None:
+        return O.nafblock(P, pre, inp)
+    x = O.layer_norm2d(inp, P[pre + "norm1.weight"], P[pre + "norm1.bias"])
+    x = F.conv2d(x, P[pre + "conv1.weight"], P[pre + "conv1.bias"])
+    x = F.conv2d(x, P[pre + "conv2.weight"], P[pre + "conv2.bias"], padding=1, groups=2 * c)
+    x = x[:, :c] * x[:, c:]
+    V, iy, ix = local_pool(x, win)
+    s = F.conv2d(V[:, :, iy][:, :, :, ix], P[pre + "sca.1.weight"], P[pre + "sca.1.bias"])
+    x = x * s
+    x = F.conv2d(x, P[pre + "conv3.weight"], P[pre + "conv3.bias"])
+    y = inp + x * P[pre + "beta"]
+    x = O.layer_norm2d(y, P[pre + "norm2.weight"], P[pre + "norm2.bias"])
+    x = F.conv2d(x, P[pre + "conv4.weight"], P[pre + "conv4.bias"])
+    x = x[:, :c] * x[:, c:]
+    x = F.conv2d(x, P[pre + "conv5.weight"], P[pre + "conv5.bias"])
+    return y + x * P[pre + "gamma"]
+
+
+def local_nafnet(P: Dict[str, torch.Tensor], inp: torch.Tensor, enc: Sequence[int], mid: int, dec: Sequence[int],
+                 kernels: Dict[str, Tuple[int, int]]) -> torch.Tensor:
+    """oracle.nafnet.nafnet with every block's SCA pooling over its own TLSC window (NAFNetLocal, NAFNet_arch.py:164-174);
+    pinned to the reference's outputs in tests/golden/tlsc_nets.npz by test_block_oracle_host.py."""
+    B, C, H, W = inp.shape
+    pad = 2 ** len(enc)
+    inp = F.pad(inp, (0, (pad - W % pad) % pad, 0, (pad - H % pad) % pad))
+    x = F.conv2d(inp, P["intro.weight"], P["intro.bias"], padding=1)
+    encs: List[torch.Tensor] = []
+    for i, n in enumerate(enc):
+        for j in range(n):
+            x = local_nafblock(P, f"encoders.{i}.{j}.", x, kernels[f"encoders.{i}.{j}."])
+        encs.append(x)
+        x = F.conv2d(x, P[f"downs.{i}.weight"], P[f"downs.{i}.bias"], stride=2)
+    for j in range(mid):
+        x = local_nafblock(P, f"middle_blks.{j}.", x, kernels[f"middle_blks.{j}."])
+    for i, n in enumerate(dec):
+        x = F.pixel_shuffle(F.conv2d(x, P[f"ups.{i}.0.weight"]), 2) + encs[::-1][i]
+        for j in range(n):
+            x = local_nafblock(P, f"decoders.{i}.{j}.", x, kernels[f"decoders.{i}.{j}."])
+    x = F.conv2d(x, P["ending.weight"], P["ending.bias"], padding=1) + inp
+    return x[:, :, :H, :W]
+
+
+def tlsc_kernels(ctor: dict, train_size: Sequence[int]) -> Dict[str, Tuple[int, int]]:
+    """{block prefix: TLSC kernel size} of NAFNetLocal(train_size=..., **ctor), from nafnet.tlsc_kernel_sizes."""
+    from lowlight_image_enhancement_amd.nafnet import tlsc_kernel_sizes
+    L = len(ctor["enc_blk_nums"])
+    ks = tlsc_kernel_sizes(train_size, L)
+    out = {f"encoders.{i}.{j}.": ks[i] for i, n in enumerate(ctor["enc_blk_nums"]) for j in range(n)}
+    out.update({f"middle_blks.{j}.": ks[L] for j in range(ctor["middle_blk_num"])})
+    out.update({f"decoders.{i}.{j}.": ks[L - 1 - i] for i, n in enumerate(ctor["dec_blk_nums"]) for j in range(n)})
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- the case table
 class Case(NamedTuple):
     name: str
@@ -208,6 +312,7 @@ class Case(NamedTuple):
     switches: dict  # executor attributes set before the forward
     plan: dict  # {"all" | "first" | "inner" | "last" | block prefix: {BlockPlan field: value}}
     seed: int = 0  # of the parameters, the image and the upstream gradient
+    train_size: Optional[Tuple[int, int, int, int]] = None  # a local case: NAFNetLocal(train_size=...), forward only
 
 
 def _flat(c, **kw):
@@ -290,6 +395,66 @@ FP32_CASES: List[Case] = [
 ]
 
 
+# ---------------------------------------------------------------------------------------------- the local cases
+# NAFNetLocal(train_size=...) run forward only (exec_forward(save=False) under no_grad): the networks and shapes of CASES
+# that differ in how the gated map reaches conv3, every one with B = 2 (the "image" error needs a second image) and with
+# a window smaller than its map.  A level-less network's kernel is (int(1.5 Ht), int(1.5 Wt)).  Without a tape C 32
+# always drops t4 and takes the fused FFN half (gemm_ffn), whatever sg_rc says.
+def _local(name, c, shape, train, switches, plan):
+    return Case(name, _flat(c), shape, switches, plan, 0, (1, 3) + tuple(train))
+
+
+_I0 = dict(tile=True, c1dw=False, rows_ffn=False, ln_fwd=True, ffn=True, drop_t4=True)
+_I1 = dict(tile=True, c1dw=False, rows_ffn=False, ln_fwd=True, ffn=False, drop_t4=False)
+_IROWS = dict(tile=False, c1dw=False, rows_ffn=True, ffn=False, drop_t4=False)
+_ILN = dict(tile=False, c1dw=False, rows_ffn=False, ln_fwd=True, ffn=False, drop_t4=False)
+_IPLAIN = dict(tile=False, c1dw=False, rows_ffn=False, ln_fwd=False, ffn=False, drop_t4=False)
+
+LOCAL_CASES: List[Case] = [
+    # name, C, (B, H, W), (Ht, Wt) -> kernel                         window on the map
+    _local("loc_c32", 32, (2, 12, 10), (4, 4), {}, {"all": _I0, **_CARRY}),                    # 6 x 6
+    _local("loc_c32_wide", 32, (2, 9, 70), (6, 2), {}, {"all": _I0, **_CARRY}),                # 9 x 3: width only
+    _local("loc_c64", 64, (2, 12, 10), (5, 3), {}, {"all": _I1, **_CARRY}),                    # 7 x 4
+    _local("loc_c64_wide", 64, (2, 9, 70), (3, 7), {}, {"all": _I1, **_CARRY}),                # 4 x 10
+    _local("loc_c64_stored_tape", 64, (2, 12, 10), (2, 5), dict(fuse_c1dw_tile=False),
+           {"all": dict(_I1, tile=False), **_CARRY}),                                          # 3 x 7
+    _local("loc_c128_rows", 128, (2, 8, 8), (3, 2), {}, {"all": _IROWS, **_CARRY}),            # 4 x 3
+    _local("loc_c128_launches", 128, (2, 8, 8), (2, 3), dict(fuse_ffn_rows=False), {"all": _ILN, **_CARRY}),  # 3 x 4
+    _local("loc_c128_hw60", 128, (2, 6, 10), (2, 5), {}, {"all": _ILN, **_CARRY}),             # 3 x 7
+    _local("loc_c256_rows", 256, (2, 8, 8), (3, 3), {}, {"all": _IROWS, **_CARRY}),            # 4 x 4
+    _local("loc_c512_c1dw_rows", 512, (2, 16, 16), (2, 11), {},
+           {"all": dict(_IROWS, c1dw=True, ln_fwd=False), **_CARRY}),                          # 3 x 16: height only
+    _local("loc_c512_rows", 512, (2, 8, 8), (2, 2), {}, {"all": dict(_IROWS, ln_fwd=False), **_CARRY}),  # 3 x 3
+    _local("loc_c1024", 1024, (2, 4, 8), (2, 3), {}, {"all": _IPLAIN, **_NO_CARRY}),           # 3 x 4
+    _local("loc_c24", 24, (2, 7, 9), (3, 4), {}, {"all": _IPLAIN, **_NO_CARRY}),               # 4 x 6
+    _local("loc_c40", 40, (2, 7, 9), (2, 3), {}, {"all": _IPLAIN, **_NO_CARRY}),               # 3 x 4
+    _local("loc_c48", 48, (2, 7, 9), (3, 5), {}, {"all": _IPLAIN, **_NO_CARRY}),               # 4 x 7
+    # U-shaped, 22 x 18 padded to 24 x 20; kernels 11 x 12, 5 x 6, 2 x 3 on the 24 x 20, 12 x 10, 6 x 5 maps
+    Case("loc_u32", CASE["u32"].ctor, (2, 22, 18), {},
+         {"encoders.0.0.": dict(_I0, carry_next=False), "decoders.1.0.": dict(_I0, carry_next=False),
+          "encoders.1.0.": dict(_I1, carry_next=False), "decoders.0.0.": dict(_I1, carry_next=False),
+          "middle_blks.0.": dict(_ILN, carry_next=False)}, 0, (1, 3, 7, 8)),
+]
+# Seeds, by the rule of _SEEDS and on the host alone: case number i of the table takes the first seed of 7000 + 100 i,
+# + 1, ... at which the stand-in is <= 1.9 x and its jittered realisations <= 2.8 x the emulation's error (u32: <= 2.9 on
+# twelve), one inner block pooling globally is >= 1.5 x the bound in both types, and the other two planted errors are
+# >= 1.5 x in fp16 (test_block_oracle_host.py asserts the conditions themselves, 2 / 3 / 1).  Windows matter more than
+# seeds: a 9 x 30 window on the 9 x 70 map left "global" at 0.3 x the bf16 bound and 9 x 7 at 0.8 - 1.0, 7 x 16 on 16 x 16
+# at 1.0 - 1.8; the table has 9 x 3 and 3 x 16 there.  Only loc_c32_wide needed a later seed than its first (7103).
+_LOCAL_SEEDS = dict(loc_c32=7000, loc_c32_wide=7103, loc_c64=7200, loc_c64_wide=7300, loc_c64_stored_tape=7400,
+                    loc_c128_rows=7500, loc_c128_launches=7600, loc_c128_hw60=7700, loc_c256_rows=7800,
+                    loc_c512_c1dw_rows=7900, loc_c512_rows=8000, loc_c1024=8100, loc_c24=8200, loc_c40=8300,
+                    loc_c48=8400, loc_u32=8500)
+LOCAL_CASES = [c._replace(seed=_LOCAL_SEEDS[c.name]) for c in LOCAL_CASES]
+LOCAL_CASE = {c.name: c for c in LOCAL_CASES}
+
+LOCAL_FP32_CASES: List[Case] = [
+    _local("loc_fp32_c20", 20, (2, 7, 9), (3, 4), {}, {})._replace(seed=2100),
+    _local("loc_fp32_c32", 32, (2, 12, 10), (4, 4), {}, {})._replace(seed=2101),
+    LOCAL_CASE["loc_u32"]._replace(name="loc_fp32_u32", plan={}, seed=2102),
+]
+
+
 def block_prefixes(ctor: dict) -> List[str]:
     """The NAFBlocks of a network in forward order."""
     out = [f"encoders.{i}.{j}." for i, n in enumerate(ctor["enc_blk_nums"]) for j in range(n)]
@@ -306,6 +471,25 @@ def expected_plan(case: Case, pre: str) -> dict:
         exp.update(case.plan.get(pos, {}))
     exp.update(case.plan.get(pre, {}))
     return exp
+
+
+def mutated_block(case: Case) -> str:
+    """The inner block the host tests plant an error in: the second of three, the middle block of the U-shaped case."""
+    return "middle_blks.0." if case.ctor["enc_blk_nums"] else "middle_blks.1."
+
+
+def block_windows(case: Case) -> Dict[str, Optional[Tuple[int, int]]]:
+    """{block prefix: the TLSC window BlockPlan.local must show} for a local case, from its kernels and map sizes."""
+    k = case.ctor
+    L = len(k["enc_blk_nums"])
+    Hp, Wp = (v + (2 ** L - v % 2 ** L) % 2 ** L for v in case.shape[1:])
+    kern = tlsc_kernels(k, case.train_size)
+    out = {}
+    for pre in block_prefixes(k):
+        kind, i = pre.split(".")[0], int(pre.split(".")[1])
+        lv = i if kind == "encoders" else (L if kind == "middle_blks" else L - 1 - i)
+        out[pre] = local_window(kern[pre], Hp >> lv, Wp >> lv)
+    return out
 
 
 def case_inputs(case: Case):
@@ -327,13 +511,34 @@ def run_case(case: Case, dtype: Optional[str], arithmetic: torch.dtype = torch.f
     storage type.  arithmetic: the dtype everything between the roundings is computed in (float64: the emulation,
     float32: the host's stand-in for the device).  jitter: a seed; every value is moved by 1 / 16 ulp x N(0, 1)
     before it is rounded, which gives one more realisation of the rounding decisions (as the device's summation orders
-    do).  Returns float64 {"out", "dx", parameter key: gradient}."""
+    do).  Returns float64 {"out", "dx", parameter key: gradient}; a local case (case.train_size) runs forward only
+    and returns {"out"}."""
     global _JITTER
     _JITTER = None if jitter is None else torch.Generator().manual_seed(jitter)
     try:
+        if case.train_size is not None:
+            with torch.no_grad():
+                return {"out": _forward(case, case_inputs(case)[1], dtype, arithmetic, mutate)}
         return _run_case(case, dtype, arithmetic, mutate)
     finally:
         _JITTER = None
+
+
+def _forward(case, x, dtype, arithmetic, mutate):
+    """The forward of `case`'s network on image batch x alone, float64 out (the local cases and the tiled frame)."""
+    sd = case_inputs(case)[0]
+    k = case.ctor
+    assert arithmetic in (torch.float64, torch.float32)
+    P = {n: v.double() for n, v in sd.items()}
+    kern = None if case.train_size is None else tlsc_kernels(k, case.train_size)
+    if dtype is None and mutate is None and arithmetic == torch.float64:
+        if kern is None:
+            return O.nafnet(P, x.double(), k["enc_blk_nums"], k["middle_blk_num"], k["dec_blk_nums"])
+        return local_nafnet(P, x.double(), k["enc_blk_nums"], k["middle_blk_num"], k["dec_blk_nums"], kern)
+    q = make_q(None if dtype is None else STORAGE[dtype])
+    p = (lambda t: t) if arithmetic == torch.float64 else (lambda t: _Round.apply(t, torch.float32, True))
+    return emulated_nafnet(P, x.double(), k["enc_blk_nums"], k["middle_blk_num"], k["dec_blk_nums"], q, mutate, p,
+                           kern).double()
 
 
 def _run_case(case, dtype, arithmetic, mutate):
@@ -355,6 +560,48 @@ def _run_case(case, dtype, arithmetic, mutate):
     res = {"out": out.detach().double(), "dx": x.grad.double()}
     res.update({n: v.grad.double() for n, v in P.items()})
     return res
+
+
+# ---------------------------------------------------------------------------------------------- the tiled frame
+# tiling.tiled_forward on the U-shaped width-32 network (the plain NAFNet: every crop is the training size): a frame a
+# little over two crops each way, 3 x 3 crops of 22 x 18 (padded to 24 x 20 inside the network) at rows 0 / 14 / 27 and
+# columns 0 / 12 / 23 -- the last ones ragged -- in chunks of 4, 4 and 1.  The seed is the first of 8600, 8601, ... that
+# meets the host conditions of the level-less cases on the blended frame (stand-in <= 1.9, three jittered <= 2.8).
+TILED = Case("tiled_u32", CASE["u32"].ctor, (1, 49, 41), {}, {}, 8600)
+TILED_OPT = {"crop_size_h": 22, "crop_size_w": 18, "max_minibatch": 4}
+
+
+def tiled_crops(lq: torch.Tensor):
+    """(crop_h, crop_w, [(i, j)], the crops by torch slicing in plan order) of frame lq under TILED_OPT."""
+    from lowlight_image_enhancement_amd.tiling import grid_plan
+    ch, cw, idxes = grid_plan(lq.shape[2], lq.shape[3], TILED_OPT)
+    at = [(d["i"], d["j"]) for d in idxes]
+    return ch, cw, at, torch.cat([lq[:, :, i:i + ch, j:j + cw] for i, j in at])
+
+
+def blend64(outs: torch.Tensor, H: int, W: int, at, ch: int, cw: int) -> torch.Tensor:
+    """grids_inverse() in float64: every pixel the mean of the crop outputs that cover it."""
+    acc = torch.zeros(1, outs.shape[1], H, W, dtype=torch.float64)
+    cnt = torch.zeros(1, 1, H, W, dtype=torch.float64)
+    for t, (i, j) in enumerate(at):
+        acc[0, :, i:i + ch, j:j + cw] += outs[t].double()
+        cnt[0, :, i:i + ch, j:j + cw] += 1
+    return acc / cnt
+
+
+def run_tiled(dtype: Optional[str], arithmetic: torch.dtype = torch.float64,
+              jitter: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """The tiled frame on the host: the oracle (dtype None) or the emulation per crop, blended in float64."""
+    global _JITTER
+    _JITTER = None if jitter is None else torch.Generator().manual_seed(jitter)
+    try:
+        lq = case_inputs(TILED)[1]
+        ch, cw, at, crops = tiled_crops(lq)
+        with torch.no_grad():
+            outs = _forward(TILED, crops, dtype, arithmetic, None)
+        return {"out": blend64(outs, lq.shape[2], lq.shape[3], at, ch, cw)}
+    finally:
+        _JITTER = None
 
 
 def bound(ref: torch.Tensor, emu: torch.Tensor) -> float:

@@ -39,7 +39,16 @@ Which case reaches which branch of the executor:
                cases) / the fp32 pair of launches (fp32 controls)
                conv5: gemm_res_ln with the next norm1 (first / inner blocks of c32_stored_t4, c32_unfolded, c64*,
                c128_launches, c128_hw60) / plain GEMM (their last blocks, c512_hw60, c1024, c24, c40, c48*, u32)
-               plan.local (TLSC): not reached -- NAFNetLocal is inference only, a taped forward raises (test_gpu_tlsc.py)
+               plan.local (TLSC, _local_sca; a taped forward raises, test_gpu_tlsc.py): the local cases below, run
+               without a tape -- ga = g (.) a[window] reaches conv3 through
+                 ffn_rows_fwd with a unit scale: loc_c128_rows, loc_c256_rows, loc_c512_rows; after c1_dw_sg_pool (its
+                   pool partials ignored): loc_c512_c1dw_rows
+                 gemm_res_ln, AM_PLAIN, no scale: after c1dw_fwd_tile (partials ignored) loc_c32, loc_c32_wide, loc_c64,
+                   loc_c64_wide, loc_u32's C 32 / 64 blocks; after GEMM + dw_sg_pool_fwd loc_c64_stored_tape,
+                   loc_c128_launches, loc_c128_hw60, loc_u32's middle block
+                 the plain GEMM + ln_fwd_nhwc: loc_c1024, loc_c24, loc_c40, loc_c48
+               and from there on conv4 / conv5 as gemm_ffn (the C 32 blocks: without a tape t4 and g2 are always
+               dropped), CM_SG + gemm_res_ln with the next norm1 / the plain GEMM, or inside ffn_rows_fwd
   _ffn_bwd_launches  dgrad_sg_rc_wg (c32, c32_wide, u32) / dgrad_sg_rc (c32_unfolded) / CM_SGBWD (the other 16-bit cases
                off the rows path) / fp32 (controls); dgrad_ln_bwd at C 32 .. 256 / GEMM + ln_bwd_nhwc (c512_hw60, c1024,
                c24, c40, c48*); chandot epilogue (c128_launches) / img_chan_dot (all others off the rows path)
@@ -64,6 +73,34 @@ The U-shaped case is the one whose inputs matter: with inputs chosen on fewer ho
 at encoders.1.0.conv1.bias[5], then 1.16 at encoders.0.0.conv2.bias[35]) while fp16 and every launch of those blocks in
 c32 / c64 passed; host realisations of the emulation alone missed the same bound at those inputs, so they were replaced
 under a stronger host condition (block_oracle._SEEDS).
+
+The local window (block_oracle.LOCAL_CASES): NAFNetLocal(train_size=...) on the networks above, B = 2, through
+exec_forward(save=False) under no_grad.  Every BlockPlan is recorded by wrapping _plan_block on the instance; per block
+plan.local must be the expected window and tile / c1dw / rows_ffn / ln_fwd / ffn / drop_t4 / carry_next what the case
+names; `out` is finite and within the same bound of the float64 local oracle (block_oracle.local_nafnet, pinned to the
+reference's NAFNetLocal on the host).  The plain NAFNet on the same weights -- the same launches, pooling globally -- must
+be OUTSIDE that bound at every case in both types, so the bound tells the window from the whole map on the device too.
+  case                 window (map)           plan
+  loc_c32              6 x 6  (12 x 10)       tile, ln_fwd, drop_t4, ffn
+  loc_c32_wide         9 x 3  (9 x 70)        the same; local in width only (k1 = h), several tiles across
+  loc_c64, _wide       7 x 4 / 4 x 10         tile, ln_fwd; no ffn / drop_t4
+  loc_c64_stored_tape  3 x 7  (12 x 10)       as loc_c64 but tile = False (fuse_c1dw_tile off)
+  loc_c128_rows        4 x 3  (8 x 8)         rows_ffn           loc_c256_rows 4 x 4, loc_c512_rows 3 x 3: the same
+  loc_c128_launches    3 x 4  (8 x 8)         ln_fwd, rows_ffn = False (fuse_ffn_rows off)
+  loc_c128_hw60        3 x 7  (6 x 10)        ln_fwd, rows_ffn = False (h * w = 60)
+  loc_c512_c1dw_rows   3 x 16 (16 x 16)       c1dw, rows_ffn; local in height only (k2 = w)
+  loc_c1024, loc_c24, loc_c40, loc_c48   3 x 4 (4 x 8), 4 x 6, 3 x 4, 4 x 7 (7 x 9)   nothing fused
+  loc_u32              11 x 12, 5 x 6, 2 x 3 on 24 x 20, 12 x 10, 6 x 5 (22 x 18 padded)   C 32 as loc_c32, C 64 as loc_c64,
+                       C 128 as loc_c128_hw60; carry_next False everywhere
+Worst error / bound of `out` measured on an MI355X (bf16, fp16), then the plain NAFNet's against the same bound:
+  loc_c32 0.250 0.246, global 4.0 36.5 | loc_c32_wide 0.250 0.267, 4.0 29.9 | loc_c64 0.279 0.249, 5.5 34.4
+  loc_c64_wide 0.250 0.356, 4.0 32.9 | loc_c64_stored_tape 0.237 0.248, 6.8 66.9 | loc_c128_rows 0.236 0.234, 5.4 45.3
+  loc_c128_launches 0.227 0.253, 9.1 70.3 | loc_c128_hw60 0.272 0.246, 6.2 52.3 | loc_c256_rows 0.260 0.319, 8.0 66.4
+  loc_c512_c1dw_rows 0.235 0.234, 4.6 33.7 | loc_c512_rows 0.258 0.271, 8.7 67.1 | loc_c1024 0.225 0.186, 6.6 37.1
+  loc_c24 0.250 0.253, 6.5 51.4 | loc_c40 0.254 0.252, 8.1 75.7 | loc_c48 0.249 0.254, 3.8 29.4
+  loc_u32 0.256 0.241, 5.2 48.3
+  fp32 controls (width 20, width 32, U-shaped): max |out - oracle| 1.3e-6, 1.2e-6, 2.4e-6 against 1e-4.
+A forward-only `out` sits at a quarter of the bound: the device's error is the emulation's own, as the host stand-in's is.
 """
 import functools
 
@@ -145,6 +182,90 @@ def test_fp32_controls(dev, case):
         worst.append((err / tol, name))
         assert err <= tol, (name, err, tol)
     print(f"[{case.name}] worst error / tolerance:", sorted(worst, reverse=True)[:5])
+
+
+# ---------------------------------------------------------------------------------------------- the local window
+_LOCAL = {c.name: c for c in bo.LOCAL_CASES + bo.LOCAL_FP32_CASES}
+
+
+@functools.lru_cache(maxsize=None)
+def _local_oracle(name):
+    torch.set_num_threads(16)
+    return bo.run_case(_LOCAL[name], None)
+
+
+@functools.lru_cache(maxsize=None)
+def _local_emulation(name, dtype):
+    torch.set_num_threads(16)
+    return bo.run_case(_LOCAL[name], dtype)
+
+
+def _inference_run(dev, case, precision, local=True):
+    """({"out"} on the host, {block prefix: BlockPlan}) of exec_forward(save=False) under no_grad: NAFNetLocal at the
+    case's train_size, or (local=False) the plain NAFNet on the same weights.  The plans are recorded by wrapping
+    _plan_block on the instance (without a tape nothing else keeps them)."""
+    from lowlight_image_enhancement_amd.nafnet import NAFNet, NAFNetLocal
+    sd, x, _ = bo.case_inputs(case)
+    net = NAFNetLocal(train_size=case.train_size, **case.ctor) if local else NAFNet(**case.ctor)
+    net.load_state_dict(sd)
+    net = net.to(dev)
+    net.precision = precision
+    for k, v in case.switches.items():
+        assert hasattr(net, k), k
+        setattr(net, k, v)
+    plans, plan_block = {}, net._plan_block
+
+    def record(W, B, h, w, c, pre, next_pre, save):
+        assert pre not in plans and not save
+        plans[pre] = plan_block(W, B, h, w, c, pre, next_pre, save)
+        return plans[pre]
+
+    net._plan_block = record
+    with torch.no_grad():
+        out, tape = net.exec_forward(x.to(dev), save=False)
+    torch.cuda.synchronize()
+    assert len(tape) == 0
+    return {"out": out.double().cpu()}, plans
+
+
+def _check_windows(case, plans):
+    assert list(plans) == bo.block_prefixes(case.ctor)
+    for pre, win in bo.block_windows(case).items():
+        assert win is not None and plans[pre].local == win, (case.name, pre, plans[pre].local, win)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("case", bo.LOCAL_CASES, ids=[c.name for c in bo.LOCAL_CASES])
+def test_local_paths_per_element(dev, case, dtype):
+    got, plans = _inference_run(dev, case, dtype)
+    _check_windows(case, plans)
+    _check_plans(case, plans)
+    _check_bound(f"{case.name} {dtype}", got, _local_oracle(case.name), _local_emulation(case.name, dtype))
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("case", bo.LOCAL_CASES, ids=[c.name for c in bo.LOCAL_CASES])
+def test_global_pooling_is_outside_the_local_bound(dev, case, dtype):
+    """The bound tells the window from the whole map on the device: the plain NAFNet on the same weights (every block
+    on the same launches but pooling globally) is outside it, in both types at every case."""
+    got, plans = _inference_run(dev, case, dtype, local=False)
+    assert all(p.local is None for p in plans.values())
+    _check_plans(case, plans)
+    assert torch.isfinite(got["out"]).all()
+    r = bo.ratios(got, _local_oracle(case.name), _local_emulation(case.name, dtype))
+    print(f"[{case.name} {dtype}] global pooling: error / local bound {r[0][0]:.2f}")
+    assert r[0][0] > 1.0, r[0]
+
+
+@pytest.mark.parametrize("case", bo.LOCAL_FP32_CASES, ids=[c.name for c in bo.LOCAL_FP32_CASES])
+def test_local_fp32_controls(dev, case):
+    """The harness (weights, windows, the recorded plans) with nothing rounded: the suite's 1e-4 for a restored image."""
+    got, plans = _inference_run(dev, case, "fp32")
+    _check_windows(case, plans)
+    assert torch.isfinite(got["out"]).all()
+    err = (got["out"] - _local_oracle(case.name)["out"]).abs().max().item()
+    print(f"[{case.name}] max |out - oracle| = {err:.3e}")
+    assert err <= 1e-4, err
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
