@@ -104,11 +104,15 @@ class AlexStack:
             feat, h, w = y, ho, wo
         return (out, tape) if save else out
 
-    def backward(self, tape, tap_grads) -> torch.Tensor:
-        """tap_grads[k]: gradient w.r.t. tap k's post-ReLU map (k = 0..4).  Returns d(prepared input) [B,H,W,8] fp32."""
+    def backward(self, tape, tap_grads, trace=None) -> torch.Tensor:
+        """tap_grads[k]: gradient w.r.t. tap k's post-ReLU map (k = 0..4).  Returns d(prepared input) [B,H,W,8] fp32.
+        trace (tests): a list that receives (stage name, tensor) for every gradient the walk stores, as
+        VGGStack.backward ("last.tap", "convI.dp" / ".pool" / ".dn" / ".tap", "d8").  None: nothing is recorded."""
         last = tape[-1][3]
         d = torch.zeros_like(last)  # pre-ReLU gradient of the last conv
         call("add_relu_masked", d, tap_grads[4].to(self.tdt).contiguous(), last, d.numel(), self.dtype)
+        if trace is not None:
+            trace.append(("last.tap", d))
         for t in range(len(tape) - 1, -1, -1):
             rec = tape[t]
             if rec[0] != "conv":
@@ -118,6 +122,8 @@ class AlexStack:
             if i == 0:
                 d8 = torch.empty(B, h, w, 8, device=d.device)
                 call("alex_conv0_input_grad", d, L["wd"], B, h, w, ho, wo, L["cout"], d8, self.dtype)
+                if trace is not None:
+                    trace.append(("d8", d8))
                 return d8
             prev = tape[t - 1]
             if prev[0] == "conv":  # conv -> ReLU -> conv: mask by the previous post map in the epilogue
@@ -125,7 +131,11 @@ class AlexStack:
                 dn = torch.empty(B, h, w, L["cin"], device=d.device, dtype=self.tdt)
                 call("conv2d_16", d, B, h, w, L["cout"], L["wt"], L["cin"], L["k"], L["k"], 1, L["pad"], None, 2, post,
                      dn, self.dtype)
+                if trace is not None:
+                    trace.append((f"conv{i}.dn", dn.clone()))
                 call("add_relu_masked", dn, tap_grads[i - 1].to(self.tdt).contiguous(), post, dn.numel(), self.dtype)
+                if trace is not None:
+                    trace.append((f"conv{i}.tap", dn))
                 d = dn
             else:  # conv -> ReLU -> pool(3, 2) -> conv
                 (_, (Bp, hp, wp, C), idx, pool_in) = prev
@@ -134,7 +144,12 @@ class AlexStack:
                      dp, self.dtype)
                 dn = torch.empty(Bp, hp, wp, C, device=d.device, dtype=self.tdt)
                 call("maxpool_k_bwd", dp, idx, pool_in, Bp, hp, wp, C, 3, 2, dn, self.dtype)
+                if trace is not None:
+                    trace.append((f"conv{i}.dp", dp))
+                    trace.append((f"conv{i}.pool", dn.clone()))
                 call("add_relu_masked", dn, tap_grads[i - 1].to(self.tdt).contiguous(), pool_in, dn.numel(), self.dtype)
+                if trace is not None:
+                    trace.append((f"conv{i}.tap", dn))
                 d = dn
         raise RuntimeError("alex backward: tape has no first conv")
 
@@ -161,14 +176,17 @@ def _trunk_taps(stack, x, save):
     return [t[tap] for tap in TAPS], tape
 
 
-def _trunk_backward(stack, tape, grads):
-    """Tap gradients (list of 5) -> d(prepared input) [B,H,W,8] fp32 for either backbone."""
+def _trunk_backward(stack, tape, grads, trace=None):
+    """Tap gradients (list of 5) -> d(prepared input) [B,H,W,8] fp32 for either backbone.  trace (tests): a list that
+    receives (stage name, tensor) for every gradient the walk stores (VGGStack.backward / AlexStack.backward)."""
     if isinstance(stack, AlexStack):
-        return stack.backward(tape, grads)
+        return stack.backward(tape, grads, trace=trace)
     last = tape[-1][3]  # relu5_3 is the VGG stack's last map: its pre-ReLU gradient
     d_last = torch.zeros_like(grads[-1])
     call("add_relu_masked", d_last, grads[-1], last, d_last.numel(), stack.dtype)
-    return stack.backward(tape, d_last, tap_grads={tap: g for tap, g in zip(TAPS[:-1], grads[:-1])})
+    if trace is not None:
+        trace.append(("last.tap", d_last))
+    return stack.backward(tape, d_last, tap_grads={tap: g for tap, g in zip(TAPS[:-1], grads[:-1])}, trace=trace)
 
 
 def _tap_distances(stack, lins, t0, t1, out, want_grad, up=None, accumulate_first=False):

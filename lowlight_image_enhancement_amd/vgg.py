@@ -153,9 +153,13 @@ class VGGStack:
         return feat, tape, tapped
 
     # ------------------------------------------------------------------ input gradient
-    def backward(self, tape, d_last_pre: torch.Tensor, tap_grads: Optional[Dict[int, torch.Tensor]] = None):
+    def backward(self, tape, d_last_pre: torch.Tensor, tap_grads: Optional[Dict[int, torch.Tensor]] = None,
+                 trace: Optional[List] = None):
         """d_last_pre: gradient w.r.t. the last conv's PRE-ReLU output (NHWC, the stack's type).  tap_grads: {relu index:
-        gradient w.r.t. that post-ReLU map} added where the walk passes it.  Returns d(prepared input) fp32 [B,H,W,8]."""
+        gradient w.r.t. that post-ReLU map} added where the walk passes it.  Returns d(prepared input) fp32 [B,H,W,8].
+        trace (tests): a list that receives (stage name, tensor) for every gradient the walk stores -- "features.N.dp"
+        (conv N's input gradient before a pool), ".pool" (after the pool backward), ".dn" (masked, conv -> conv), ".tap"
+        (after add_relu_masked; the value it overwrote is traced as a copy) and "d8".  None: nothing is recorded."""
         tap_grads = tap_grads or {}
         d = d_last_pre
         n = len(tape)
@@ -168,14 +172,21 @@ class VGGStack:
             if prev is None:  # first conv: gradient of the prepared input
                 d8 = torch.empty(B, h, w, L["cin"], device=d.device)
                 call("conv3x3_bf16", d, B, h, w, L["cout"], L["wt"], L["cin"], None, 1, None, d8, 0, self.dtype)
+                if trace is not None:
+                    trace.append(("d8", d8))
                 return d8
+            name = f"features.{L['idx']}" if trace is not None else None
             if prev[0] == "conv":  # conv -> ReLU -> conv: mask by the previous post map in the epilogue
                 post = prev[3]
                 dn = torch.empty(B, h, w, L["cin"], device=d.device, dtype=self.tdt)
                 call("conv3x3_bf16", d, B, h, w, L["cout"], L["wt"], L["cin"], None, 2, post, dn, self.ydt, self.dtype)
                 tg = tap_grads.get(prev[1]["idx"] + 1)
+                if trace is not None:
+                    trace.append((name + ".dn", dn if tg is None else dn.clone()))
                 if tg is not None:  # + d(tap) * relu mask
                     call("add_relu_masked", dn, tg.to(self.tdt).contiguous(), post, dn.numel(), self.dtype)
+                    if trace is not None:
+                        trace.append((name + ".tap", dn))
                 d = dn
             else:  # conv -> ReLU -> pool -> conv
                 (_, (Bp, hp, wp, C), idx, pool_in) = prev
@@ -185,8 +196,13 @@ class VGGStack:
                 call("maxpool2_bwd", dp, idx, pool_in, Bp, hp, wp, C, dn, self.dtype)
                 conv_before = tape[k - 2]
                 tg = tap_grads.get(conv_before[1]["idx"] + 1)
+                if trace is not None:
+                    trace.append((name + ".dp", dp))
+                    trace.append((name + ".pool", dn if tg is None else dn.clone()))
                 if tg is not None:
                     call("add_relu_masked", dn, tg.to(self.tdt).contiguous(), pool_in, dn.numel(), self.dtype)
+                    if trace is not None:
+                        trace.append((name + ".tap", dn))
                 d = dn
         raise RuntimeError("VGG backward: tape has no conv layer")
 

@@ -212,10 +212,11 @@ def _composition(a, b, w, dtype):
 
 
 @pytest.mark.parametrize("net,layer,C,precision", [("alex", 0, 64, "fp32"), ("alex", 1, 192, "fp32"),
-                                                   ("vgg", 3, 512, "fp32"), ("vgg", 2, 256, "bf16")])
+                                                   ("vgg", 3, 512, "fp32"), ("vgg", 2, 256, "bf16"),
+                                                   ("vgg", 2, 256, "fp16")])
 def test_tap_map_against_float64_torch(dev, net, layer, C, precision):
-    """bf16 taps widen to fp32 exactly and the kernel's arithmetic is fp32 either way, so the same bound holds on the
-    taps as stored."""
+    """bf16 / fp16 taps widen to fp32 exactly and the kernel's arithmetic is fp32 either way, so the same bound holds on
+    the taps as stored."""
     from lowlight_image_enhancement_amd._lib import call
     from lowlight_image_enhancement_amd.lpips import _trunk_taps
     m, _, lins = _model(net, True, precision)
@@ -225,7 +226,7 @@ def test_tap_map_against_float64_torch(dev, net, layer, C, precision):
     x0, x1 = (torch.rand(2, 3, H, W, generator=g) * 2 - 1).to(dev), (torch.rand(2, 3, H, W, generator=g) * 2 - 1).to(dev)
     a, b = _trunk_taps(stack, x0, False)[0][layer], _trunk_taps(stack, x1, False)[0][layer]
     N, h, w, Ca = a.shape
-    assert Ca == C and a.dtype == (torch.float32 if precision == "fp32" else torch.bfloat16)
+    assert Ca == C and a.dtype == {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[precision]
     out = torch.full((N, h, w), float("nan"), device=dev)
     call("lpips_tap_map", a, b, dlins[layer], N, h * w, C, out, stack.dtype)
     an, bn = a.float().cpu().permute(0, 3, 1, 2), b.float().cpu().permute(0, 3, 1, 2)  # the GPU's own taps, read back
