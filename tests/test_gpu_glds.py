@@ -2,8 +2,10 @@
 MFMA sequence, so every output must be bitwise identical (NBP_GLDS=0 selects the register-staged kernel, unset the
 DMA ring with its depth chosen per launch; the knob is read per launch).  Covers every A mode the DMA path serves (plain, per-image scale,
 space-to-depth gather, 3x3 im2col with zero padding), the C modes of the deep-level GEMMs, ragged M / N, a K tail
-(K % 64 != 0), both 16-bit types, and the fused-LayerNorm entries.  Accuracy against float64 is covered by the
-existing GEMM tests, which run on the DMA path by default."""
+(K % 64 != 0), both 16-bit types, and the fused-LayerNorm entries.  Accuracy against float64: the plain / scaled modes
+in the GEMM tests of test_gpu_parity.py and test_gpu_fp16.py (which run on the DMA path by default), the
+space-to-depth gather and the depth-to-space scatter per element in tests/test_gpu_level_convs.py (both kernels, every
+tile shape and ring depth these two modes reach)."""
 import os
 
 import pytest
@@ -80,22 +82,23 @@ def test_glds_scale_simplegate(dev, dt, M, C, rows):
     run_modes(fn)
 
 
+@pytest.mark.parametrize("dt", [1, 2])
 @pytest.mark.parametrize("B,gh,gw,cs", [(16, 16, 16, 256), (2, 32, 24, 64), (3, 5, 7, 128)])
-def test_glds_space_to_depth(dev, B, gh, gw, cs):
+def test_glds_space_to_depth(dev, dt, B, gh, gw, cs):
     """down conv (2x2 / stride 2 as a space-to-depth GEMM, K = 4 cs) and the up conv's depth-to-space epilogue."""
     from lowlight_image_enhancement_amd._lib import call
     gen = torch.Generator(device=dev).manual_seed(B * gh + cs)
-    x = torch.randn(B, 2 * gh, 2 * gw, cs, device=dev, generator=gen).to(torch.bfloat16)
+    x = torch.randn(B, 2 * gh, 2 * gw, cs, device=dev, generator=gen).to(DT[dt])
     M, K, N = B * gh * gw, 4 * cs, 2 * cs
-    W = (torch.randn(N, K, device=dev, generator=gen) / K ** 0.5).to(torch.bfloat16)
+    W = (torch.randn(N, K, device=dev, generator=gen) / K ** 0.5).to(DT[dt])
     bias = torch.randn(N, device=dev, generator=gen)
-    y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
-    Wu = (torch.randn(4 * cs, N, device=dev, generator=gen) / N ** 0.5).to(torch.bfloat16)
-    up = torch.empty(B, 2 * gh, 2 * gw, cs, device=dev, dtype=torch.bfloat16)
+    y = torch.empty(M, N, device=dev, dtype=DT[dt])
+    Wu = (torch.randn(4 * cs, N, device=dev, generator=gen) / N ** 0.5).to(DT[dt])
+    up = torch.empty(B, 2 * gh, 2 * gw, cs, device=dev, dtype=DT[dt])
 
     def fn():
-        call("gemm_bf16", x, K, 1, None, 1, 1, W, K, y, N, 0, 1, M, N, K, gh, gw, cs, bias, None, None, None)
-        call("gemm_bf16", y, N, 0, None, 1, 1, Wu, N, up, N, 1, 1, M, 4 * cs, N, gh, gw, cs, None, None, None, None)
+        call("gemm_bf16", x, K, 1, None, 1, dt, W, K, y, N, 0, dt, M, N, K, gh, gw, cs, bias, None, None, None)
+        call("gemm_bf16", y, N, 0, None, 1, dt, Wu, N, up, N, 1, dt, M, 4 * cs, N, gh, gw, cs, None, None, None, None)
         return y, up
     run_modes(fn)
 
